@@ -9,7 +9,10 @@ the batch: ExtractPhone + EstimatePitch + pitch transform + GenerateWaveform
 collective inside a hop; weights are broadcast from rank 0 over RCCL at load).  Inputs are resident
 in HBM before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value (frames/s), unit, higher_is_better, dtype, ms_per_step of the
+--steps timed steps, and the workload's configuration.  A plain run does nothing else (set-up, device warm-up,
+--warmup steps, the timed steps, --dump-outputs); with --full the line also carries what takes runs of its own,
+among them:
   roofline      -- dominant kernel of the chain: algorithmic FLOP/s (or B/s) vs gfx950 peak, from
                    HIP-event timing on the library's own stream (BeatriceBatch_ProfileKernels)
   cpu_baseline  -- the CPU oracle (oracle/, a port of the frozen spec -- NOT the proprietary
@@ -452,6 +455,25 @@ def latency_b1(model_dir, hops=100000, warm=2000, paced_hops=1500):
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(directory, outputs, rank):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (DIR/<name>_rank<r>.npy on ranks other than 0).  First axis = stream; an
+    array larger than its share of DUMP_BYTES_MAX keeps a fixed, seeded sample of its streams, whose indices go to <name>_streams.npy."""
+    os.makedirs(directory, exist_ok=True)
+    suffix = "_rank%d" % rank if rank else ""
+    share = DUMP_BYTES_MAX // len(outputs)
+    for name, t in outputs.items():
+        x = t.detach().float().cpu().numpy()
+        row_bytes = x[0].nbytes
+        if x.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(x.shape[0], max(1, (share - 8 * x.shape[0]) // row_bytes), replace=False))
+            x = x[rows]
+            np.save(os.path.join(directory, name + "_streams" + suffix + ".npy"), rows.astype(np.float64))
+        np.save(os.path.join(directory, name + suffix + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -480,7 +502,15 @@ def main():
     ap.add_argument("--device-warm-ms", type=float, default=1000.0,
                     help="milliseconds of the workload's own steps (untimed, drained) before the warm-up steps, so that a run of a few milliseconds "
                          "executes at the clocks of a device that has been converting, not at an idle one's (+5 %% at 20 steps); 0 = off; stated in config")
-    ap.add_argument("--no-extras", action="store_true", help="skip cpu_baseline / B=1 latency / kernel profile")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the bench measures: the host's own work per step, the tick launch's "
+                         "roofline, the steady state of a short run and (unless --no-extras) the per-kernel table, the other batch sizes, "
+                         "hop counts and modes, morphing, B=1 latency, measured peaks and the CPU baseline.  Without it a run sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip cpu_baseline / B=1 latency / kernel profile")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them handed its caller (the output slot of every stream) "
+                         "as DIR/<name>.npy, float32; the inputs depend on the arguments only, so two builds can be compared output for output")
     ap.add_argument("--total-streams", type=int, default=None,
                     help="strong scaling: this many streams in total, split evenly over the GPUs (default: --streams per GPU, weak scaling)")
     ap.add_argument("--placement", choices=("round-robin", "speaker-affine"), default=None,
@@ -492,6 +522,8 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, run one all-reduce over gloo and exit (CPU check that --gpus N launches N ranks)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # --gpus N without a launcher: start N ranks of this script under torch.distributed.run (one process per GPU)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -590,6 +622,7 @@ def main():
     for s in range(B):
         product.BeatriceBatch_SetTargetSpeaker(batch.h, s, current_speaker[s])
     product.BeatriceBatch_FlushSpeaker(batch.h, -1)
+    first_speaker = list(current_speaker)   # (configs[3]'s schedule below moves current_speaker ahead of the steps)
     if a.config == 3:
         product.BeatriceBatch_SetVQNumNeighbors(batch.h, -1, 4)
 
@@ -656,16 +689,18 @@ def main():
     if a.config == 3:
         schedule_until(a.warmup + a.steps + 700)
 
-    fed = [0]   # steps fed so far (the resident ring's slot and configs[3]'s switch schedule follow it)
+    fed = [0]   # steps fed so far (the resident ring's slot follows it)
+    origin = [0]   # the step the streams last started afresh at (configs[3]'s switch schedule counts from it)
 
     def step(_unused=None):
         i = fed[0]
         fed[0] += 1
         if a.config == 3:
-            if i >= len(schedule):
-                schedule_until(i + 1)
-            if schedule[i] is not None:   # one call for all of the step's switches
-                product.BeatriceBatch_SetTargetSpeakers(batch.h, *schedule[i])
+            j = i - origin[0]
+            if j >= len(schedule):
+                schedule_until(j + 1)
+            if schedule[j] is not None:   # one call for all of the step's switches
+                product.BeatriceBatch_SetTargetSpeakers(batch.h, *schedule[j])
         if a.config == 4 and tick48:
             rc = product.BeatriceBatch_ConvertBlocks48kDevice(batch.h, None, None, 2)
         elif a.config == 4:
@@ -687,9 +722,19 @@ def main():
             for _ in range(64):
                 step()
             product.BeatriceBatch_Synchronize(batch.h)
+        # How many steps ran above depends on the build's speed, and the streams carry state from step to step: every stream starts
+        # afresh (on its first speaker; configs[3]'s schedule from its first step), then 256 steps keep the device busy as above, so that
+        # what the timed steps compute depends on the arguments only (--dump-outputs)
+        if a.config == 3 and product.BeatriceBatch_SetTargetSpeakers(batch.h, B, (ctypes.c_int * B)(*range(B)), (ctypes.c_int * B)(*first_speaker)):
+            raise SystemExit("SetTargetSpeakers failed")
+        if product.BeatriceBatch_ResetStream(batch.h, -1):
+            raise SystemExit("ResetStream failed")
+        origin[0] = fed[0]
+        for _ in range(4):
+            for _ in range(64):
+                step()
+            product.BeatriceBatch_Synchronize(batch.h)
         torch.cuda.synchronize()
-        if a.config == 3:
-            schedule_until(fed[0] + a.warmup + a.steps + 700)
     for i in range(a.warmup):
         step(i)
     product.BeatriceBatch_Synchronize(batch.h)
@@ -710,13 +755,22 @@ def main():
         dist.barrier()
         elapsed = shard.max_over_ranks(elapsed, world, dist, torch, "cuda")
     per_rank_elapsed = shard.gather_over_ranks(own_elapsed, world, dist, torch, "cuda") if world > 1 else [own_elapsed]
-    # the host's own work per step, measured where the device cannot push back: 12 steps (fewer than the 16 settings snapshots the
-    # library lets the host run ahead) into a drained pipeline, enqueue time only
-    t_probe = time.perf_counter()
-    for i in range(12):
-        step(a.warmup + a.steps + i)
-    host_work_s = (time.perf_counter() - t_probe) / 12
-    product.BeatriceBatch_Synchronize(batch.h)
+    if a.dump_outputs:   # the last timed step's output slot: resident slots are taken in turn from the binding on, the others reuse slot 0
+        last = (fed[0] - 1) % n_cycle
+        if a.config == 4:
+            outputs = {"out48k": d_out48[last if tick48 else 0]}   # [B][H][2][480] @48 kHz, stereo
+        else:
+            outputs = {"out24k": d_out[last if resident else 0]}   # [B][H*240] @24 kHz
+        dump_outputs(a.dump_outputs, outputs, rank)
+    host_work_s = None
+    if a.full:
+        # the host's own work per step, measured where the device cannot push back: 12 steps (fewer than the 16 settings snapshots the
+        # library lets the host run ahead) into a drained pipeline, enqueue time only
+        t_probe = time.perf_counter()
+        for i in range(12):
+            step(a.warmup + a.steps + i)
+        host_work_s = (time.perf_counter() - t_probe) / 12
+        product.BeatriceBatch_Synchronize(batch.h)
     out_rms = float((d_out48 if a.config == 4 else d_out).float().pow(2).mean().sqrt().item())
 
     if rank == 0:
@@ -752,13 +806,14 @@ def main():
             "in_flight": ({"steps": int(product.BeatriceBatch_TickStages(batch.h)), "audio_ms_per_stream": int(product.BeatriceBatch_TickStages(batch.h)) * H * 10,
                            "wall_ms": round(int(product.BeatriceBatch_TickStages(batch.h)) * 1e3 * elapsed / a.steps, 3)} if (tick or tick48) else None),
             "host_enqueue_ms_per_step": round(1e3 * enqueue_s / a.steps, 4),   # (includes waiting for the device once the host is 16 settings snapshots ahead)
-            "host_work_ms_per_step": round(1e3 * host_work_s, 4),               # (12 steps into a drained pipeline: the host's own work)
             "per_rank_frames_per_s": [round(B * a.steps * H / e, 1) for e in per_rank_elapsed],   # (a straggler shows; `value` uses the MAX-reduced time)
         }
+        if host_work_s is not None:
+            res["host_work_ms_per_step"] = round(1e3 * host_work_s, 4)         # (12 steps into a drained pipeline: the host's own work)
         tick_roof = None
         if tick48:  # configs[4]: the wrapper kernels run beside each tick launch; per-kernel figures below are of the chain in order
             product.BeatriceBatch_BindResidentIO48k(batch.h, None, None, 0, 0)
-        if tick:
+        if tick and a.full:
             # the dominant kernel of the headline IS the tick launch: refill the pipeline, then time 64 more launches between
             # one pair of HIP events on the batch's stream (BeatriceBatch_TimeTickLaunch)
             stages = product.BeatriceBatch_TickStages(batch.h)
@@ -801,7 +856,7 @@ def main():
                 product.BeatriceBatch_Synchronize(batch.h)
                 res["steady_state"] = {"steps": 600, "frames_per_s": round(B * H * 600 / (time.perf_counter() - t1), 1),
                                        "note": "same loop, 600 steps: fill and drain (%d ticks) amortised" % (stages - 1)}
-        if not a.no_extras:
+        if a.full and not a.no_extras:
             # per-kernel timing with HIP events on the library's own stream (eager, 10 launches per bracket), chain in order
             if tick:
                 product.BeatriceBatch_EnableTickPipeline(batch.h, 0)

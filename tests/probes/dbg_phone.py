@@ -1,6 +1,6 @@
 import importlib.util, os, sys, tempfile
 import numpy as np
-REPO="/root/repo"
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 spec = importlib.util.spec_from_file_location("beatrice_vst_amd", os.path.join(REPO, "beatrice-vst_amd", "__init__.py"))
 bv = importlib.util.module_from_spec(spec); sys.modules["beatrice_vst_amd"]=bv; spec.loader.exec_module(bv)
 sys.path.insert(0, os.path.join(REPO,"tools")); import make_model

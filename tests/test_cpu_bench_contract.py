@@ -31,6 +31,7 @@ def test_committed_bench_line_has_the_contract_fields():
 def test_bench_help_and_pmc_summary(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
     # two launches of one kernel: FETCH_SIZE 100 and 300 KiB, WRITE_SIZE 10 and 30 KiB -> (2 x 200 + 20) KiB per launch
     for name, vals in (("FETCH_SIZE", (100, 300)), ("WRITE_SIZE", (10, 30))):
         d = tmp_path / ("pmc_r1_" + name)

@@ -120,19 +120,61 @@ def test_host_library_exports_every_declared_symbol():
     assert exported == names, sorted(exported ^ names)
 
 
-def test_declarations_match_reference_header():
-    """Every function name the reference header declares is declared by ours (runs only where the
-    reference is mounted; the GPU box skips it)."""
-    ref = "/root/reference/lib/beatricelib/beatrice.h"
-    if not os.path.exists(ref):
-        pytest.skip("reference not mounted")
+_C_TYPE_WORDS = {"void", "char", "short", "int", "long", "float", "double", "signed", "unsigned", "const", "volatile", "struct", "enum"}
+
+
+def _param_type(decl):
+    """`const float* input` -> `const float*`: the type of a parameter (or a return type), without the parameter's name and without a
+    qualifier of the parameter itself, which is not part of the function's type (`T* const` -> `T*`, `const int` -> `int`)."""
+    tok = re.findall(r"\w+|\*", decl)
+    if len(tok) > 1 and re.match(r"\w", tok[-1]) and tok[-1] not in _C_TYPE_WORDS and tok[-2] not in ("struct", "enum"):
+        tok = tok[:-1]
+    if tok[-1:] == ["const"]:
+        tok = tok[:-1]
+    elif "*" not in tok:
+        tok = [t for t in tok if t != "const"]
+    return " ".join(tok).replace(" *", "*")
+
+
+def _abi_view(header, compiler, std):
+    """What a caller binds from a beatricelib header, as `compiler` reads it in `std`: {function: its type as
+    `return(param,...)`}, {typedef name: `struct tag` / `enum tag`} and {error code: value}."""
     import subprocess
-    ours = subprocess.check_output(["gcc", "-E", "-I" + os.path.join(REPO, "include"),
-                                    os.path.join(REPO, "include", "beatrice_abi.h")]).decode()
-    theirs = open(ref).read()
-    want = set(re.findall(r"\b(Beatrice20(?:a2|b1|rc0)_[A-Za-z0-9]+)\s*\(", theirs))
-    have = set(re.findall(r"\b(Beatrice20(?:a2|b1|rc0)_[A-Za-z0-9]+)\s*\(", ours))
-    assert want == have and len(want) == 77
+    text = subprocess.check_output([compiler, std, "-E", "-P", "-x", "c" if compiler == "gcc" else "c++", header]).decode()
+    text = " ".join(text.split())
+    funcs, typedefs, codes = {}, {}, {}
+    for st in re.split(r"[;{}]", text):
+        m = re.fullmatch(r"\s*(.*?)\b(Beatrice20(?:a2|b1|rc0)_\w+)\s*\((.*)\)\s*", st)
+        if m:
+            funcs[m.group(2)] = "%s(%s)" % (_param_type(m.group(1)), ",".join(_param_type(p) for p in m.group(3).split(",")))
+    for kind, tag, alias in re.findall(r"typedef (struct|enum) (\w+)\s*(?:\{[^}]*\})?\s*(\w+)\s*;", text):
+        typedefs[alias] = kind + " " + tag
+    value = -1
+    for e in re.search(r"enum Beatrice_ErrorCode\s*\{([^}]*)\}", text).group(1).split(","):
+        name, _, v = e.strip().partition("=")
+        if name:
+            value = int(v) if v.strip() else value + 1
+            codes[name.strip()] = value
+    return funcs, typedefs, codes
+
+
+def _fingerprint(function_type):
+    import hashlib
+    return hashlib.sha256(function_type.encode()).hexdigest()[:16] if function_type is not None else None
+
+
+def _reference_abi():
+    """The reference header's C-ABI, recorded with _abi_view (tests/golden/reference_abi.json: names, a fingerprint of every
+    function's type, typedefs, error codes)."""
+    import json
+    return json.load(open(os.path.join(GOLD, "reference_abi.json")))
+
+
+def test_declarations_match_reference_header():
+    """Every function name the reference header declares is declared by ours, and no other."""
+    want = set(_reference_abi()["functions"])
+    have = set(_abi_view(os.path.join(REPO, "include", "beatrice_abi.h"), "gcc", "-std=c11")[0])
+    assert want == have and len(want) == 77, sorted(want ^ have)
 
 
 def test_legacy_generations_link_and_decline(product):
@@ -244,33 +286,32 @@ def test_model_toml_has_the_schema_the_reference_reader_asks_for(model_dir):
 
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c11"), ("g++", "-std=c++20")])
 def test_prototypes_agree_with_reference_header(tmp_path, compiler, std):
-    """Types, not just names: the reference header and ours in ONE translation unit.  A C compiler rejects two
-    declarations of a function whose return or argument types differ ("conflicting types"), so a clean compile proves
-    all 77 prototypes and the constants agree.  Our copy goes in with its enum definition removed (the reference's is
-    in scope; its enumerator values are checked by static assertions).  Runs where the reference is mounted."""
-    ref = "/root/reference/lib/beatricelib/beatrice.h"
-    if not os.path.exists(ref):
-        pytest.skip("reference not mounted")
+    """Types, not just names: every prototype of our header, as `compiler` reads it in `std`, has the type the reference header
+    gives that function (return and parameter types, against the fingerprints recorded from the reference header), the opaque
+    types are the reference's typedefs, and the error codes have its values.  A translation unit that takes the address of all
+    77 functions compiles cleanly and refers to them by their plain C names (C linkage, in C++ too)."""
     import subprocess
-    ours = open(os.path.join(REPO, "include", "beatrice_abi.h")).read()
-    stripped, n = re.subn(r"typedef enum Beatrice_ErrorCode \{.*?\} Beatrice_ErrorCode;", "", ours, flags=re.S)
-    assert n == 1
-    values = dict(re.findall(r"(Beatrice_k[A-Za-z]+) = (\d+)", ours))
-    assert len(values) == 5
-    (tmp_path / "ours_no_enum.h").write_text(stripped)
-    sa = "_Static_assert" if compiler == "gcc" else "static_assert"
-    tu = '#include "%s"\n#include "ours_no_enum.h"\n' % ref
-    tu += "".join('%s(%s == %s, "%s");\n' % (sa, k, v, k) for k, v in values.items())
-    tu += "int main(void) { return 0; }\n"
+    ref = _reference_abi()
+    header = os.path.join(REPO, "include", "beatrice_abi.h")
+    funcs, typedefs, codes = _abi_view(header, compiler, std)
+    bad = {k: funcs.get(k) for k, fp in ref["functions"].items() if _fingerprint(funcs.get(k)) != fp}
+    assert not bad, bad
+    assert {k: typedefs.get(k) for k in ref["typedefs"]} == ref["typedefs"]
+    assert codes == ref["error_codes"] and len(codes) == 5
     src = tmp_path / ("tu.c" if compiler == "gcc" else "tu.cc")
-    src.write_text(tu)
-    out = subprocess.run([compiler, std, "-fsyntax-only", "-Wall", "-Werror", "-I" + str(tmp_path), str(src)],
+    src.write_text('#include "beatrice_abi.h"\nvoid* const fns[] = {%s};\n' % ", ".join("(void*)&" + k for k in sorted(ref["functions"])))
+    obj = tmp_path / "tu.o"
+    out = subprocess.run([compiler, std, "-c", "-Wall", "-Werror", "-I" + os.path.join(REPO, "include"), str(src), "-o", str(obj)],
                          capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-3000:]
+    undefined = set(subprocess.check_output(["nm", "-u", str(obj)]).decode().split())
+    assert set(ref["functions"]) <= undefined, sorted(set(ref["functions"]) - undefined)[:5]
     # and the check has teeth: one changed argument type must be caught
-    broken = stripped.replace("void G##_SetMinQuantizedPitch(G##_PitchContext1* ctx, int min_quantized_pitch);",
-                              "void G##_SetMinQuantizedPitch(G##_PitchContext1* ctx, long min_quantized_pitch);")
-    assert broken != stripped
-    (tmp_path / "ours_no_enum.h").write_text(broken)
-    out = subprocess.run([compiler, std, "-fsyntax-only", "-I" + str(tmp_path), str(src)], capture_output=True, text=True)
-    assert out.returncode != 0
+    ours = open(header).read()
+    broken = ours.replace("void G##_SetMinQuantizedPitch(G##_PitchContext1* ctx, int min_quantized_pitch);",
+                          "void G##_SetMinQuantizedPitch(G##_PitchContext1* ctx, long min_quantized_pitch);")
+    assert broken != ours
+    (tmp_path / "broken.h").write_text(broken)
+    funcs = _abi_view(str(tmp_path / "broken.h"), compiler, std)[0]
+    assert {k for k, fp in ref["functions"].items() if _fingerprint(funcs.get(k)) != fp} == \
+        {"Beatrice20%s_SetMinQuantizedPitch" % g for g in ("a2", "b1", "rc0")}

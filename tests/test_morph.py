@@ -58,12 +58,20 @@ def test_spherical_mean_matches_golden(host_lib):
         assert np.array_equal(out, g["out_%d" % i]), "case %d max-abs %g" % (i, np.abs(out - g["out_%d" % i]).max())
 
 
+def _recorded():
+    """the reference solver's results for the cases below, recorded by tools/make_golden.py (used where oracle/_ref is not built;
+    where it is, the recording must still be what it computes)"""
+    return np.load(os.path.join(GOLD, "reference_cases.npz"))
+
+
 def test_spherical_mean_matches_reference_live(host_lib):
     ref = wrapperlib.ref_wrapper()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
-    for pts, w, order, limit, updates in _cases():
-        a = _mean(ref.lib, "ref_spherical_average", pts, w, order, limit, updates)
+    g = _recorded()
+    for i, (pts, w, order, limit, updates) in enumerate(_cases()):
+        a = int(g["mean_it_%d" % i][0]), g["mean_out_%d" % i]
+        if ref is not None:
+            live = _mean(ref.lib, "ref_spherical_average", pts, w, order, limit, updates)
+            assert live[0] == a[0] and np.array_equal(live[1], a[1]), "recording out of date: case %d" % i
         b = _mean(host_lib, "BeatriceHost_SphericalMean", pts, w, order, limit, updates)
         assert a[0] == b[0] and np.array_equal(a[1], b[1])
 
@@ -73,8 +81,15 @@ def test_morph_branch_matches_emulation_with_reference_solver(bv, oracle, host_l
     additive mean on the first hop after a weight change, K/V token means over four hops (96 tokens
     each), re-registration on the fifth, then one K/V block per hop."""
     ref = wrapperlib.ref_wrapper()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
+    g = _recorded()
+
+    def ref_mean(key, pts, pruned, order):   # the reference's SphericalAverage: live where oracle/_ref is built, else as recorded
+        want = g[key]
+        if ref is not None:
+            live = _mean(ref.lib, "ref_spherical_average", pts, pruned, order, min(n_spk, 8), 4)[1]
+            assert np.array_equal(live, want), "recording out of date: " + key
+        return want
+
     sr, block, hops = 48000, 480, 16
     x = wrapperlib.test_signal(block * hops, sr, seed=77)
     weights = np.zeros(256, np.float32)
@@ -106,13 +121,11 @@ def test_morph_branch_matches_emulation_with_reference_solver(bv, oracle, host_l
     def hop(in160, out240, _u):
         c = state["counter"]
         if c == 0:
-            _, add = _mean(ref.lib, "ref_spherical_average", t.additive[:n_spk], pruned, order, min(n_spk, 8), 4)
-            t.additive[n_spk] = add
+            t.additive[n_spk] = ref_mean("morph_additive", t.additive[:n_spk], pruned, order)
             st.a.SetAdditiveSpeakerEmbedding(m.embed, bv.fptr(t.additive[n_spk]), st.ec, st.wc)
         if c < 4:
             for i in range(384 * c // 4, 384 * (c + 1) // 4):
-                _, tok = _mean(ref.lib, "ref_spherical_average", np.ascontiguousarray(t.kv[:n_spk, i, :]), pruned, order, min(n_spk, 8), 4)
-                t.kv[n_spk, i] = tok
+                t.kv[n_spk, i] = ref_mean("morph_kv_%d" % i, np.ascontiguousarray(t.kv[:n_spk, i, :]), pruned, order)
         elif c == 4:
             st.a.RegisterKeyValueSpeakerEmbedding(m.embed, bv.fptr(t.kv[n_spk]), st.ec)
             st.kv_count = 0

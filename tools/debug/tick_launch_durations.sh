@@ -1,5 +1,6 @@
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/pt -o k -- python $GRAFT_REPO_ROOT/bench.py --no-extras --steps 300 --warmup 20 > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/pt -o k -- python "$ROOT/bench.py" --full --no-extras --steps 300 --warmup 20 > /dev/null 2>&1
 python - "$(find /tmp/pt -name 'k_kernel_trace.csv' | head -1)" <<'PY'
 import csv, sys
 d = sorted(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in csv.DictReader(open(sys.argv[1])) if "table_kernel" in r["Kernel_Name"])

@@ -1,11 +1,12 @@
 #!/bin/bash
 # per-launch durations of a tick run (rocprofv3 kernel trace):
 #   tools/debug/tick_prof.sh [env assignments...] [-- bench.py arguments]
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pd
 envs=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do envs+=("$1"); shift; done
 [ "$1" = "--" ] && shift
-timeout 240 env "${envs[@]}" rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pd -o t -- python /root/repo/bench.py --steps 200 --warmup 5 --no-extras "$@" > /tmp/pd_bench.json 2>/dev/null
+timeout 240 env "${envs[@]}" rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pd -o t -- python "$ROOT/bench.py" --full --steps 200 --warmup 5 --no-extras "$@" > /tmp/pd_bench.json 2>/dev/null
 f="$(find /tmp/pd -name 't_kernel_stats.csv' | head -1)"
 [ -n "$f" ] || { echo "no kernel stats produced"; exit 1; }
 python - "$f" "${envs[*]} $*" <<PY

@@ -1,6 +1,7 @@
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/p20
-rocprofv3 --kernel-trace --output-format csv -d /tmp/p20 -o k -- python $GRAFT_REPO_ROOT/bench.py --no-extras --steps 20 --warmup 5 > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/p20 -o k -- python "$ROOT/bench.py" --full --no-extras --steps 20 --warmup 5 > /dev/null 2>&1
 python - "$(find /tmp/p20 -name 'k_kernel_trace.csv' | head -1)" <<'PY'
 import csv, sys
 rows = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in csv.DictReader(open(sys.argv[1])) if "table_kernel" in r["Kernel_Name"])

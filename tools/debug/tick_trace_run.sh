@@ -5,5 +5,5 @@
 [ -f "$(dirname "$0")/../../build_variants/lib_meas.so" ] && export BEATRICE_HIP_LIB="$(cd "$(dirname "$0")/../.." && pwd)/build_variants/lib_meas.so"
 export BEATRICE_HIP_TICK_DROP=${1:-0}
 shift
-BEATRICE_HIP_TICK_TRACE=/tmp/tick_trace.txt python bench.py --steps 100 --warmup 30 --no-extras "$@" > /dev/null 2>&1
+BEATRICE_HIP_TICK_TRACE=/tmp/tick_trace.txt python bench.py --full --steps 100 --warmup 30 --no-extras "$@" > /dev/null 2>&1
 python tools/debug/tick_trace.py /tmp/tick_trace.txt

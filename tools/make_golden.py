@@ -83,5 +83,45 @@ def main():
         print("%-24s %7d bytes" % (f, os.path.getsize(os.path.join(GOLD, f))))
 
 
+def reference_cases():
+    """reference_cases.npz: the reference library's results (oracle/_ref/libref_wrapper.so) for exactly the cases of the tests that
+    call it -- tests/test_wrapper_oracle.py::test_chain_matches_reference_live, tests/test_morph.py::test_spherical_mean_matches_reference_live
+    and ::test_morph_branch_matches_emulation_with_reference_solver --, which compare against it where oracle/_ref cannot be built.
+    Run where it can:  make -C oracle && python tools/make_golden.py reference_cases"""
+    ref = wrapperlib.ref_wrapper()
+    if ref is None:
+        raise SystemExit("oracle/_ref/libref_wrapper.so missing: run `make -C oracle` where the reference exists")
+    import importlib.util
+    import test_morph
+    import test_wrapper_oracle
+    g = {}
+    for sr, block in test_wrapper_oracle.LIVE_CASES:
+        g["chain_%d_%d" % (sr, block)] = ref.run_chain(sr, test_wrapper_oracle.live_chain_input(sr), block)
+    for i, (pts, w, order, limit, updates) in enumerate(test_morph._cases()):
+        it, out = test_morph._mean(ref.lib, "ref_spherical_average", pts, w, order, limit, updates)
+        g["mean_it_%d" % i], g["mean_out_%d" % i] = np.array([it], np.int32), out
+    # the morph branch: the tests' model (tests/conftest.py model_dir), weights 0.5 / 0.3 / 0.2 on speakers 0, 1, 2
+    spec = importlib.util.spec_from_file_location("beatrice_vst_amd", os.path.join(REPO, "beatrice-vst_amd", "__init__.py"))
+    bv = importlib.util.module_from_spec(spec)
+    sys.modules["beatrice_vst_amd"] = bv
+    spec.loader.exec_module(bv)
+    oracle = bv.Abi(os.path.join(REPO, "oracle", "libbeatrice_oracle.so"))
+    pruned, order = np.array([0.5, 0.3, 0.2], np.float32), np.array([0, 1, 2], np.int32)
+    with tempfile.TemporaryDirectory() as d:
+        make_model.make_model(d, n_speakers=3)
+        m = bv.Models(oracle, d)
+        t, n = m.tables, m.tables.n_speakers
+        g["morph_additive"] = test_morph._mean(ref.lib, "ref_spherical_average", t.additive[:n], pruned, order, min(n, 8), 4)[1]
+        for i in range(t.kv.shape[1]):
+            g["morph_kv_%d" % i] = test_morph._mean(ref.lib, "ref_spherical_average", np.ascontiguousarray(t.kv[:n, i, :]), pruned, order,
+                                                    min(n, 8), 4)[1]
+        m.close()
+    np.savez_compressed(os.path.join(GOLD, "reference_cases.npz"), **g)
+    print("reference_cases.npz %d bytes, %d arrays" % (os.path.getsize(os.path.join(GOLD, "reference_cases.npz")), len(g)))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["reference_cases"]:
+        reference_cases()
+    else:
+        main()

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES; do
   rm -rf "$OUT/pmc_$C"
-  rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o pmc -- python "$ROOT/bench.py" --no-extras --steps 200 --warmup 5 > /dev/null 2>&1
+  rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o pmc -- python "$ROOT/bench.py" --full --no-extras --steps 200 --warmup 5 > /dev/null 2>&1
   CSV=$(find "$OUT/pmc_$C" -name 'pmc_counter_collection.csv' | head -1)
   mkdir -p "$OUT/pmc_r1_$C"
   [ -n "$CSV" ] && cp "$CSV" "$OUT/pmc_r1_$C/pmc_counter_collection.csv"

@@ -53,7 +53,7 @@ def main(root, out):
     import bench   # csrc_sha1: the sources these passes ran on; bench.py quotes the summary only while they are unchanged
     commit = os.popen("git -C %s rev-parse --short HEAD 2>/dev/null" % os.path.dirname(os.path.abspath(bench.__file__))).read().strip()
     json.dump({"csrc_sha1": bench.csrc_sha1(), "commit": commit or "(no .git on the GPU box: see csrc_sha1)",
-               "note": "bytes per launch = (2 x FETCH_SIZE + WRITE_SIZE) x 1024; bench.py --no-extras, B=256; tick launch: mean over full ticks",
+               "note": "bytes per launch = (2 x FETCH_SIZE + WRITE_SIZE) x 1024; bench.py --full --no-extras, B=256; tick launch: mean over full ticks",
                "kernels": res}, open(out, "w"), indent=1, sort_keys=True)
     for k, r in sorted(res.items(), key=lambda kv: -kv[1]["hbm_bytes_per_launch"])[:12]:
         print("%8.2f MB  %s" % (r["hbm_bytes_per_launch"] / 1e6, k[:120]))

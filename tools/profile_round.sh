@@ -14,17 +14,17 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 
-timeout 900 python "$ROOT/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 python "$ROOT/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 400 "$OUT/bench.err"
 # the driver's own flags, five times on this box (a 20-step run is 5 ms of launches and follows the box's clocks: VERDICT r05 item 3 asks for the median)
 for i in 1 2 3 4 5; do timeout 300 python "$ROOT/bench.py" --steps 20 --warmup 5 --no-extras > "$OUT/bench_driver_flags_steps20_run$i.json" 2> /dev/null; done
-timeout 600 python "$ROOT/bench.py" --steps 20 --warmup 5 > "$OUT/bench_driver_flags_steps20.json" 2> /dev/null
-timeout 300 python "$ROOT/bench.py" --config 3 --no-extras > "$OUT/bench_config3.json" 2> /dev/null
-timeout 300 python "$ROOT/bench.py" --config 4 --no-extras > "$OUT/bench_config4.json" 2> /dev/null
-timeout 300 python "$ROOT/bench.py" --streams 1024 --no-extras > "$OUT/bench_B1024.json" 2> /dev/null
+timeout 600 python "$ROOT/bench.py" --full --steps 20 --warmup 5 > "$OUT/bench_driver_flags_steps20.json" 2> /dev/null
+timeout 300 python "$ROOT/bench.py" --full --config 3 --no-extras > "$OUT/bench_config3.json" 2> /dev/null
+timeout 300 python "$ROOT/bench.py" --full --config 4 --no-extras > "$OUT/bench_config4.json" 2> /dev/null
+timeout 300 python "$ROOT/bench.py" --full --streams 1024 --no-extras > "$OUT/bench_B1024.json" 2> /dev/null
 
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o k -- \
-  python "$ROOT/bench.py" --no-extras --steps 300 --warmup 20 > "$OUT/bench_under_rocprof.json" 2> /dev/null
+  python "$ROOT/bench.py" --full --no-extras --steps 300 --warmup 20 > "$OUT/bench_under_rocprof.json" 2> /dev/null
 STATS=$(find "$OUT/prof" -name 'k_kernel_stats.csv' | head -1)
 [ -n "$STATS" ] && cp "$STATS" "$OUT/kernel_stats_B256_tick.csv"
 # the stats average of the tick launch mixes full ticks with the partly filled ones of fill and drain: split them
@@ -39,7 +39,7 @@ print("tick launches %d: mean of all %.2f us; full ticks (>= 0.9 x third quartil
 PY
 rm -rf "$OUT/prof"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o k -- \
-  python "$ROOT/bench.py" --no-extras --pipeline off --steps 200 --warmup 20 > /dev/null 2>&1
+  python "$ROOT/bench.py" --full --no-extras --pipeline off --steps 200 --warmup 20 > /dev/null 2>&1
 STATS=$(find "$OUT/prof" -name 'k_kernel_stats.csv' | head -1)
 [ -n "$STATS" ] && cp "$STATS" "$OUT/kernel_stats_B256_in_order.csv"
 rm -rf "$OUT/prof"
@@ -48,7 +48,7 @@ rm -rf "$OUT/prof"
 
 for C in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES; do
   timeout 600 rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o pmc -- \
-    python "$ROOT/bench.py" --no-extras --steps 200 --warmup 5 > /dev/null 2>&1
+    python "$ROOT/bench.py" --full --no-extras --steps 200 --warmup 5 > /dev/null 2>&1
   CSV=$(find "$OUT/pmc_$C" -name 'pmc_counter_collection.csv' | head -1)
   mkdir -p "$OUT/pmc_r1_$C"
   [ -n "$CSV" ] && cp "$CSV" "$OUT/pmc_r1_$C/pmc_counter_collection.csv"
@@ -58,7 +58,7 @@ python "$ROOT/tools/pmc_summary.py" "$OUT" "$OUT/pmc_traffic.json"
 # the summary goes where bench.py looks (profiles/, under the round's name) on this box; the caller copies it there in the repo as well
 ROUND=$(echo "$TAG" | cut -c1-3)
 cp "$OUT/pmc_traffic.json" "$ROOT/profiles/${ROUND}_pmc_traffic.json"
-timeout 900 python "$ROOT/bench.py" > "$OUT/bench_with_traffic.json" 2> /dev/null
+timeout 900 python "$ROOT/bench.py" --full > "$OUT/bench_with_traffic.json" 2> /dev/null
 # keep the merge-back small: raw traces stay on the box
 rm -rf "$OUT/prof" "$OUT/pmc_FETCH_SIZE" "$OUT/pmc_WRITE_SIZE" "$OUT/pmc_SQ_VALU_MFMA_BUSY_CYCLES"
 for C in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES; do
