@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "abi_objects.h"
+#include "batch_modes.h"
 #include "beatrice_batch.h"
 #include "tick.hip.h"
 #include "wrapper.hip.h"
@@ -664,9 +665,19 @@ bool step_device(BeatriceBatch* b, const float* d_in, float* d_out) {
 
 #include "batch_tick.hip.h"      // tick mode: table, per-tick host work, drain, enable
 
+using modes::Entry;
+modes::Flags flags_of(const BeatriceBatch* b) {
+  return {b->tk.on, b->hs.on, b->r48.on, b->rb.on, b->rb.ragged, b->silent.on, b->pipelined, b->io_slots > 0, b->H, b->wrap.ready, b->rw.ready};
+}
+// The opening of every BeatriceBatch_* entry point: the batch's device for the call's duration, -2 for a missing or unhealthy batch; then
+// -1 for what the batch's mode refuses (batch_modes.h), before anything is drained, synchronised, bound or written.
+#define BATCH_OPEN(b) const DeviceScope dev_((b) ? (b)->device : -1); if (!(b) || !(b)->ok) return -2
+#define BATCH_GATE(b, entry) if (!modes::allowed(entry, flags_of(b))) return -1
+#define BATCH_ENTER(b, entry) BATCH_OPEN(b); BATCH_GATE(b, entry)
+
 template <class F>
 int for_streams(BeatriceBatch* b, int stream, F f) {
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (stream < -1 || stream >= b->B) return -1;
   const int lo = stream < 0 ? 0 : stream, hi = stream < 0 ? b->B : stream + 1;
   for (int s = lo; s < hi; ++s) { f(b->cfg[s]); sync_stream_arrays(b, s); }
@@ -972,8 +983,7 @@ bool project_speakers(BeatriceBatch* b, int first, int count) {
 
 int BeatriceBatch_SetSpeakerTables(BeatriceBatch* b, int n, const float* codebooks, const float* additive, const float* formant,
                                    const float* kv) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (n < 1 || n > b->max_speakers || !codebooks || !additive || !formant || !kv) return -1;
   bool ok = sync_all(b) &&
             hip_ok(hipMemcpy(b->d_cb_raw, codebooks, sizeof(float) * n * B_CODEBOOK * B_PHONE_CH, hipMemcpyHostToDevice), "cb") &&
@@ -993,8 +1003,7 @@ int BeatriceBatch_SetSpeakerTables(BeatriceBatch* b, int n, const float* codeboo
 // rank that read the file): [0] codebooks [S][512][128], [1] additive [S][256], [2] formant [9][256], [3] key/value
 // [S][384][128]; then BeatriceBatch_ProjectSpeakerTables(b, n) does what SetSpeakerTables does after its upload.
 int BeatriceBatch_SpeakerTablesDevice(BeatriceBatch* b, void** d_ptrs, size_t* n_bytes) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (!d_ptrs || !n_bytes) return -1;
   const size_t S = (size_t)b->max_speakers;
   d_ptrs[0] = b->d_cb_raw; n_bytes[0] = sizeof(float) * S * B_CODEBOOK * B_PHONE_CH;
@@ -1004,8 +1013,7 @@ int BeatriceBatch_SpeakerTablesDevice(BeatriceBatch* b, void** d_ptrs, size_t* n
   return 0;
 }
 int BeatriceBatch_ProjectSpeakerTables(BeatriceBatch* b, int n) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (n < 1 || n > b->max_speakers) return -1;
   if (!sync_all(b) || !hip_ok(hipDeviceSynchronize(), "tables sync")) return -2;
   b->n_speakers = n;
@@ -1017,8 +1025,7 @@ int BeatriceBatch_ProjectSpeakerTables(BeatriceBatch* b, int n) {
 }
 
 int BeatriceBatch_UpdateSpeaker(BeatriceBatch* b, int spk, const float* codebook, const float* additive, const float* kv) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (spk < 0 || spk >= b->max_speakers) return -1;
   bool ok = sync_all(b);
   if (codebook) ok = ok && hip_ok(hipMemcpy(b->d_cb_raw + (size_t)spk * B_CODEBOOK * B_PHONE_CH, codebook, sizeof(float) * B_CODEBOOK * B_PHONE_CH, hipMemcpyHostToDevice), "cb1");
@@ -1077,8 +1084,7 @@ static int morph_into(BeatriceBatch* b, int slot, const float* weights, int n_we
   return 0;
 }
 int BeatriceBatch_MorphSpeaker(BeatriceBatch* b, int slot, const float* weights, int n_weights, unsigned seed) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (const int rc = morph_into(b, slot, weights, n_weights, seed)) return rc;
   // streams already on this entry re-install its key/value blocks, one per hop, like after a speaker switch
   for (StreamCfg& c : b->cfg) if (c.target_speaker == slot) { c.kv_set_count = 0; c.kv_delay = 0; }
@@ -1096,8 +1102,7 @@ int BeatriceBatch_MorphSpeaker(BeatriceBatch* b, int slot, const float* weights,
 // faster than every eight hops needs anyway -- the reference never installs new blocks while the weights keep moving, and
 // neither do streams here: each call restarts their four-hop wait).
 int BeatriceBatch_MorphSpeakerStaged(BeatriceBatch* b, int slot, int from_slot, const float* weights, int n_weights, unsigned seed) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (from_slot < 0 || from_slot >= b->max_speakers || from_slot == slot) return -1;
   if (slot >= 0 && slot < b->max_speakers)
     for (const StreamCfg& c : b->cfg) {
@@ -1123,8 +1128,7 @@ int BeatriceBatch_MorphSpeakerStaged(BeatriceBatch* b, int slot, int from_slot, 
 // the codebook lottery's engine of one stream (or of all, -1): std::mt19937(seed), e.g. a value derived from the
 // stream's global identity when streams are sharded over several batches / GPUs
 int BeatriceBatch_SeedLottery(BeatriceBatch* b, int stream, unsigned seed) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (stream < -1 || stream >= b->B) return -1;
   for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? b->B : stream + 1); ++s) b->lottery[s].seed(seed);
   b->lottery_seeded = true;  // a later BeatriceBatch_MorphSpeaker keeps these engines
@@ -1132,8 +1136,7 @@ int BeatriceBatch_SeedLottery(BeatriceBatch* b, int stream, unsigned seed) {
 }
 // copies the morphed entry's raw embeddings back (test / inspection hook; any pointer may be NULL)
 int BeatriceBatch_GetSpeakerEmbeddings(BeatriceBatch* b, int speaker, float* additive, float* key_value) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (speaker < 0 || speaker >= b->max_speakers) return -1;
   bool ok = sync_all(b);
   if (additive) ok = ok && hip_ok(hipMemcpy(additive, b->d_add_raw + (size_t)speaker * B_HID, sizeof(float) * B_HID, hipMemcpyDeviceToHost), "add");
@@ -1145,8 +1148,7 @@ int BeatriceBatch_GetSpeakerEmbeddings(BeatriceBatch* b, int speaker, float* add
 // processor_core_2.cc:431-466: codebook + additive switch at once, K/V re-registered and installed
 // one block per following hop.
 int BeatriceBatch_SetTargetSpeaker(BeatriceBatch* b, int stream, int speaker) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (speaker < 0 || speaker >= b->max_speakers) return -1;
   const int r = for_streams(b, stream, [&](StreamCfg& c) {
     c.target_speaker = speaker; c.codebook_speaker = speaker; c.additive_speaker = speaker; c.kv_set_count = 0; c.kv_delay = 0;
@@ -1159,8 +1161,7 @@ int BeatriceBatch_SetTargetSpeaker(BeatriceBatch* b, int stream, int speaker) {
 // 64 rotating speakers) pays the bookkeeping of the pending key/value installs once, not once per stream.  All or nothing: an
 // invalid pair changes nothing.
 int BeatriceBatch_SetTargetSpeakers(BeatriceBatch* b, int n, const int* streams, const int* speakers) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (n < 0 || (n > 0 && (!streams || !speakers))) return -1;
   for (int i = 0; i < n; ++i)
     if (streams[i] < 0 || streams[i] >= b->B || speakers[i] < 0 || speakers[i] >= b->max_speakers) return -1;
@@ -1191,58 +1192,48 @@ int BeatriceBatch_FlushSpeaker(BeatriceBatch* b, int stream) {
 }
 // processor_core_2.cc:468-481
 int BeatriceBatch_SetFormantShift(BeatriceBatch* b, int stream, double shift) {
-  const DeviceScope dev_(b ? b->device : -1);
   shift = std::min(std::max(shift, -2.0), 2.0);
   const int idx = (int)std::round(shift * 2.0 + 4.0);
   return for_streams(b, stream, [&](StreamCfg& c) { c.formant_index = idx; });
 }
 // processor_core_2.cc:585-590
 int BeatriceBatch_SetVQNumNeighbors(BeatriceBatch* b, int stream, int k) {
-  const DeviceScope dev_(b ? b->device : -1);
   k = std::min(std::max(k, 0), 8);
   if (b) b->vq_dirty = true;
   return for_streams(b, stream, [&](StreamCfg& c) { c.vq_k = k; });
 }
 int BeatriceBatch_SetMinSourcePitch(BeatriceBatch* b, int stream, double note) {
-  const DeviceScope dev_(b ? b->device : -1);
   const int q = midi_to_bin(note);
   return for_streams(b, stream, [&](StreamCfg& c) { c.min_q = q; });
 }
 int BeatriceBatch_SetMaxSourcePitch(BeatriceBatch* b, int stream, double note) {
-  const DeviceScope dev_(b ? b->device : -1);
   const int q = midi_to_bin(note);
   return for_streams(b, stream, [&](StreamCfg& c) { c.max_q = q; });
 }
 // processor_core_2.cc:483-486, 534-559
 int BeatriceBatch_SetPitchShift(BeatriceBatch* b, int stream, double v) {
-  const DeviceScope dev_(b ? b->device : -1);
   v = std::min(std::max(v, -24.0), 24.0);
   return for_streams(b, stream, [&](StreamCfg& c) { c.pitch.pitch_shift = v; });
 }
 int BeatriceBatch_SetAverageSourcePitch(BeatriceBatch* b, int stream, double v) {
-  const DeviceScope dev_(b ? b->device : -1);
   v = std::min(std::max(v, 0.0), 128.0);
   return for_streams(b, stream, [&](StreamCfg& c) { c.pitch.average_source_pitch = v; });
 }
 int BeatriceBatch_SetIntonationIntensity(BeatriceBatch* b, int stream, double v) {
-  const DeviceScope dev_(b ? b->device : -1);
   return for_streams(b, stream, [&](StreamCfg& c) { c.pitch.intonation_intensity = v; });
 }
 int BeatriceBatch_SetPitchCorrection(BeatriceBatch* b, int stream, double v) {
-  const DeviceScope dev_(b ? b->device : -1);
   v = std::min(std::max(v, 0.0), 1.0);
   return for_streams(b, stream, [&](StreamCfg& c) { c.pitch.pitch_correction = v; });
 }
 int BeatriceBatch_SetPitchCorrectionType(BeatriceBatch* b, int stream, int type) {
-  const DeviceScope dev_(b ? b->device : -1);
   if (type < 0 || type > 1) return -1;
   return for_streams(b, stream, [&](StreamCfg& c) { c.pitch.pitch_correction_type = type; });
 }
 // processor_core_2.cc:258-291: fresh contexts, then speaker (all four blocks at once) and the other
 // settings re-applied -- here the settings persist per stream, only the state is zeroed.
 int BeatriceBatch_ResetStream(BeatriceBatch* b, int stream) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (stream < -1 || stream >= b->B) return -1;
   const int lo = stream < 0 ? 0 : stream, hi = stream < 0 ? b->B : stream + 1;
   bool ok = !(b->pipelined || b->tk.on) || sync_all(b);  // later stages of earlier steps may still be running (own streams / later ticks)
@@ -1258,10 +1249,7 @@ int BeatriceBatch_ResetStream(BeatriceBatch* b, int stream) {
 
 // ---- per-hop ------------------------------------------------------------------------------------
 int BeatriceBatch_ConvertFramesDevice(BeatriceBatch* b, const float* d_in, float* d_out) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (b->io_slots > 0 && (d_in || d_out)) return -1;   // resident I/O is bound: NULL, NULL (the step reads and writes its slot)
-  if (b->hs.on || b->r48.on || b->rb.on) return -1;     // host streaming and the wrappers around the ticks feed the pipeline through their own entry points
+  BATCH_ENTER(b, d_in || d_out ? Entry::ConvertFramesDevice_ptrs : Entry::ConvertFramesDevice_NULL);
   return step_device(b, d_in, d_out) ? 0 : -2;
 }
 // Resident I/O: the caller keeps n_slots steps of input and output on the device,
@@ -1269,13 +1257,10 @@ int BeatriceBatch_ConvertFramesDevice(BeatriceBatch* b, const float* d_in, float
 // step k (BeatriceBatch_ConvertFramesDevice(b, NULL, NULL)) reads slot k mod n_slots and writes the same
 // slot of d_out, with no copy: the slot index lives next to the step counter in device memory and is
 // advanced by the last kernel, so the captured graph stays valid.  NULL pointers unbind.
-int BeatriceBatch_BindResidentIO(BeatriceBatch* b, const float* d_in, float* d_out, int n_slots) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+// (bind_io: the binding itself, for the modes that bind slots of their own on their way in and out)
+static int bind_io(BeatriceBatch* b, const float* d_in, float* d_out, int n_slots) {
   const bool bind = d_in != nullptr || d_out != nullptr;
   if (bind && (!d_in || !d_out || n_slots < 1)) return -1;
-  if (b->tk.on) return -1;  // leave tick mode first
-  if (bind && b->silent.on) return -1;  // the silent-block rule is an in-order mode of the 48 kHz blocks: switch it off first
   if (!set_io_mapped(b, false) || !sync_all(b)) return -2;
   b->io_host = 0;
   drop_graph(b);  // kernel arguments change
@@ -1294,11 +1279,15 @@ int BeatriceBatch_BindResidentIO(BeatriceBatch* b, const float* d_in, float* d_o
   const int zero = 0;  // the next step starts at slot 0
   return hip_ok(hipMemcpy(b->d_hop_next + 1, &zero, sizeof(int), hipMemcpyHostToDevice), "slot0") ? 0 : -2;
 }
+int BeatriceBatch_BindResidentIO(BeatriceBatch* b, const float* d_in, float* d_out, int n_slots) {
+  BATCH_ENTER(b, d_in || d_out ? Entry::BindResidentIO_bind : Entry::BindResidentIO_unbind);
+  return bind_io(b, d_in, d_out, n_slots);
+}
 
 int BeatriceBatch_ConvertFrames(BeatriceBatch* b, const float* in, float* out) {
   const DeviceScope dev_(b ? b->device : -1);
   if (!b || !b->ok) { if (b && out) std::memset(out, 0, sizeof(float) * b->B * b->H * B_OUT_HOP); return -2; }
-  if (b->io_slots > 0 || b->tk.on) return -1;  // resident I/O is bound
+  BATCH_GATE(b, Entry::ConvertFrames);
   const size_t n_in = (size_t)b->B * b->H * B_IN_HOP, n_out = (size_t)b->B * b->H * B_OUT_HOP;
   b->want_mapped = true;
   bool ok = set_io_mapped(b, true);
@@ -1321,14 +1310,12 @@ int BeatriceBatch_InjectTeamTimeout(BeatriceBatch* b) {
   return 0;
 }
 int BeatriceBatch_Synchronize(BeatriceBatch* b) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   return sync_all(b) ? 0 : -2;
 }
 
 int BeatriceBatch_SetStream(BeatriceBatch* b, void* hip_stream) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   (void)sync_all(b);
   drop_graph(b);
   if (b->owns_stream) (void)hipStreamDestroy(b->stream);
@@ -1338,8 +1325,7 @@ int BeatriceBatch_SetStream(BeatriceBatch* b, void* hip_stream) {
 }
 void* BeatriceBatch_GetStream(const BeatriceBatch* b) { return b ? b->stream : nullptr; }
 int BeatriceBatch_EnableGraph(BeatriceBatch* b, int enable) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   (void)sync_all(b);
   b->use_graph = enable != 0;
   if (!b->use_graph) drop_graph(b);
@@ -1352,10 +1338,7 @@ int BeatriceBatch_EnableGraph(BeatriceBatch* b, int enable) {
 // runs on a second stream.  Same results; a step's output is complete when BeatriceBatch_Synchronize returns
 // (or, stream-ordered, on BeatriceBatch_GetWaveStream).  Off by default: everything in order on one stream.
 int BeatriceBatch_EnableTickPipeline(BeatriceBatch* b, int enable) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (b->hs.on || b->r48.on || b->rb.on) return -1;  // those modes own the tick pipeline: leave them instead
-  if (enable && b->silent.on) return -1;              // (see BeatriceBatch_EnableSilentBlockRule)
+  BATCH_ENTER(b, enable ? Entry::EnableTickPipeline_1 : Entry::EnableTickPipeline_0);
   return tick_enable(b, enable != 0);
 }
 int BeatriceBatch_TickStages(const BeatriceBatch* b) { return b ? b->tk.plan.count() : 0; }
@@ -1363,10 +1346,8 @@ int BeatriceBatch_TickStages(const BeatriceBatch* b) { return b ? b->tk.plan.cou
 // between one pair of HIP events on the batch's stream; returns the mean duration per launch and its algorithmic work.
 // Call with the pipeline full (at least BeatriceBatch_TickStages steps fed) for the steady-state figure.
 int BeatriceBatch_TimeTickLaunch(BeatriceBatch* b, int ticks, float* us_per_launch, double* flops, double* bytes) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (!b->tk.on || ticks < 1 || ticks > 64 || !us_per_launch) return -1;
-  if (b->hs.on || b->r48.on || b->rb.on) return -1;   // plain tick mode only (those modes feed the pipeline through their own entry points)
+  BATCH_ENTER(b, Entry::TimeTickLaunch);
+  if (ticks < 1 || ticks > 64 || !us_per_launch) return -1;
   // ONE pair of events around `ticks` back-to-back launches (an event pair per launch adds two commands between
   // consecutive launches and reads ~5 us long against rocprofv3's kernel durations); the figure includes the boundary
   // between two ticks, which belongs to the launch's cost
@@ -1397,12 +1378,11 @@ extern "C" int BeatriceBatchMeas_TickOnlyTypes(BeatriceBatch* b, unsigned long l
 }
 #endif
 int BeatriceBatch_EnablePipelining(BeatriceBatch* b, int enable) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (b->tk.on) return -1;
+  BATCH_OPEN(b);
+  modes::Flags f = flags_of(b);
+  if (enable < 1) f.silent = false;   // (the rule stands in the way of n >= 1 only: switching off is the cell of the same mode without the rule)
+  if (!modes::allowed(Entry::EnablePipelining, f) || enable < 0 || enable > BeatriceBatch::kMaxStages) return -1;
   if (!set_io_mapped(b, false) || !sync_all(b)) return -2;
-  if (enable < 0 || enable > BeatriceBatch::kMaxStages) return -1;
-  if (enable >= 1 && b->silent.on) return -1;  // (see BeatriceBatch_EnableSilentBlockRule)
   drop_graph(b);  // stages are captured on the streams they will run on
   set_plan(b, enable == 1 ? 2 : enable);  // 1 = the default depth
   for (int s = 1; s < b->n_stages && b->pipelined; ++s)  // every stream takes a hardware queue: only those in use exist
@@ -1412,8 +1392,7 @@ int BeatriceBatch_EnablePipelining(BeatriceBatch* b, int enable) {
 void* BeatriceBatch_GetWaveStream(const BeatriceBatch* b) { return b ? wave_stream(b) : nullptr; }
 // Captures the hipGraphs of the current mode now (nothing is executed), so that the first steps do not pay for it.
 int BeatriceBatch_Prepare(BeatriceBatch* b) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (b->vq_dirty) { update_vq_mode(b); b->vq_dirty = false; }
   if (!b->use_graph) return 0;
   bool ok = true;
@@ -1428,8 +1407,7 @@ float* BeatriceBatch_DeviceOutput(BeatriceBatch* b) {
 }
 
 int BeatriceBatch_GetIntermediates(BeatriceBatch* b, float* phone, int* q_raw, int* q, float* feat) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   bool ok = sync_all(b);
   if (phone) {  // the phone vectors of the last step sit in one of the three step slots of a per-stream ring
     const size_t row = sizeof(float) * b->H * B_PHONE_CH;
@@ -1474,9 +1452,8 @@ struct ProfileHook : LaunchHook {
 
 int BeatriceBatch_ProfileKernels(BeatriceBatch* b, int repeats, int max_entries, char* names, int* launches, double* mean_us,
                                  double* flops, double* bytes) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (repeats < 1 || max_entries < 1 || !names || !launches || !mean_us || !flops || !bytes || b->tk.on) return -1;
+  BATCH_ENTER(b, Entry::ProfileKernels);
+  if (repeats < 1 || max_entries < 1 || !names || !launches || !mean_us || !flops || !bytes) return -1;
   if (!sync_all(b)) return -2;
   advance_kv(b);
   if (b->vq_dirty) { update_vq_mode(b); b->vq_dirty = false; }
@@ -1509,9 +1486,8 @@ int BeatriceBatch_ProfileKernels(BeatriceBatch* b, int repeats, int max_entries,
 }
 
 int BeatriceBatch_TimeSteps(BeatriceBatch* b, int steps, float* ms) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok || steps < 1 || !ms) return b && b->ok ? -1 : -2;
-  if (b->hs.on || b->r48.on || b->rb.on) return -1;   // (as BeatriceBatch_ConvertFramesDevice: those modes feed the pipeline through their own entry points)
+  BATCH_ENTER(b, Entry::TimeSteps);
+  if (steps < 1 || !ms) return -1;
   bool ok = sync_all(b) && hip_ok(hipEventRecord(b->ev0, b->stream), "ev0");
   for (int i = 0; i < steps && ok; ++i) ok = step_device(b, nullptr, nullptr);
   ok = ok && hip_ok(hipEventRecord(b->ev1, wave_stream(b)), "ev1") && hip_ok(hipEventSynchronize(b->ev1), "evsync") &&

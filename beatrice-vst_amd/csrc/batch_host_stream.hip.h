@@ -63,8 +63,8 @@ void host_stream_free(BeatriceBatch* b) {
 }  // namespace
 extern "C" {
 int BeatriceBatch_EnableHostStreaming(BeatriceBatch* b, int enable) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
+  if (enable) BATCH_GATE(b, Entry::EnableHostStreaming_1);
   BeatriceBatch::HostStream& h = b->hs;
   if ((enable != 0) == h.on) return 0;
   if (!enable) {
@@ -72,11 +72,10 @@ int BeatriceBatch_EnableHostStreaming(BeatriceBatch* b, int enable) {
     (void)hipStreamSynchronize(h.s_in); (void)hipStreamSynchronize(h.s_out);
     const int rc = tick_enable(b, false);
     if (rc) return rc;
-    const int rb = BeatriceBatch_BindResidentIO(b, nullptr, nullptr, 0);
+    const int rb = bind_io(b, nullptr, nullptr, 0);
     host_stream_free(b);
     return rb;
   }
-  if (b->H > tick::kMaxHops || b->io_slots > 0 || b->tk.on || b->pipelined || b->silent.on) return -1;   // (the in-order silent-block rule: switch it off first)  // one or two hops per step (buffers are [B][H x 160] -> [B][H x 240]); no other binding or pipelining
   h.n_slots = b->tk.plan.count() + 8;
   const size_t n_in = (size_t)b->B * b->H * B_IN_HOP, n_out = (size_t)b->B * b->H * B_OUT_HOP;
   bool ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&h.d_in), sizeof(float) * n_in * h.n_slots), "hs d_in") &&
@@ -92,8 +91,8 @@ int BeatriceBatch_EnableHostStreaming(BeatriceBatch* b, int enable) {
   h.tick_of_ev.assign(tick::kRing, -1);
   h.mapped = bhip::meas_env("BEATRICE_HIP_HS_COPIES") == nullptr;   // A/B switch: copies on two more streams instead
   if (ok && h.mapped) std::memset(h.h_in, 0, sizeof(float) * n_in * h.n_slots);
-  ok = ok && BeatriceBatch_BindResidentIO(b, h.mapped ? h.h_in : h.d_in, h.mapped ? h.h_out : h.d_out, h.n_slots) == 0 && tick_enable(b, true) == 0;
-  if (!ok) { (void)tick_enable(b, false); (void)BeatriceBatch_BindResidentIO(b, nullptr, nullptr, 0); host_stream_free(b); return -2; }
+  ok = ok && bind_io(b, h.mapped ? h.h_in : h.d_in, h.mapped ? h.h_out : h.d_out, h.n_slots) == 0 && tick_enable(b, true) == 0;
+  if (!ok) { (void)tick_enable(b, false); (void)bind_io(b, nullptr, nullptr, 0); host_stream_free(b); return -2; }
   h.pending.clear();
   h.fed = 0;
   h.rec[0] = h.rec[1] = -1;
@@ -104,10 +103,9 @@ int BeatriceBatch_HostStreamDelay(const BeatriceBatch* b) { return b ? b->tk.pla
 // in: [B][160] host; out: [B][240] host.  Returns 1 when `out` received the samples of the step fed
 // BeatriceBatch_HostStreamDelay() calls ago, 0 while the pipeline is still filling (out untouched), < 0 on error.
 int BeatriceBatch_StreamFrames(BeatriceBatch* b, const float* in, float* out) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_ENTER(b, Entry::StreamFrames);
   BeatriceBatch::HostStream& h = b->hs;
-  if (!h.on || !in || !out) return -1;
+  if (!in || !out) return -1;
   const size_t n_in = (size_t)b->B * b->H * B_IN_HOP, n_out = (size_t)b->B * b->H * B_OUT_HOP;
   const int slot = b->io_host;  // the slot the tick about to be fed reads and, pipeline depth later, writes
   if (h.mapped) {
@@ -147,10 +145,9 @@ int BeatriceBatch_StreamFrames(BeatriceBatch* b, const float* in, float* out) {
 // After the last StreamFrames: hands back the next step still inside the pipeline (running ticks without input as
 // needed); returns 1 with `out` filled, 0 when nothing is pending.
 int BeatriceBatch_StreamFlush(BeatriceBatch* b, float* out) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_ENTER(b, Entry::StreamFrames);   // (the table's row is "StreamFrames / StreamFlush")
   BeatriceBatch::HostStream& h = b->hs;
-  if (!h.on || !out) return -1;
+  if (!out) return -1;
   if (h.pending.empty()) return 0;
   const size_t n_out = (size_t)b->B * b->H * B_OUT_HOP;
   while (!h.pending.front().fetched)

@@ -56,28 +56,26 @@ static void silent_release(BeatriceBatch* b) {
 // state, its wrapper state (filter histories, the pending 10 ms of the FIFO), its pending key/value installs and its codebook
 // lottery stand still, as if the block had never existed.
 int BeatriceBatch_EnableSilentBlockRule(BeatriceBatch* b, int enable) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
+  // (G, P refuse both directions: a resident-block binding owns the rule's flags while it is bound -- BindResidentBlocksRagged names the
+  // streams whose FIFO did not fire through silent.next; switching the rule off underneath it would advance every stream on every fired
+  // step while the key/value installs and the codebook lottery still skip the flagged ones)
+  BATCH_GATE(b, enable ? Entry::EnableSilentBlockRule_1 : Entry::EnableSilentBlockRule_0);
   BeatriceBatch::SilentRule& sr = b->silent;
-  // a resident-block binding around the ticks owns the rule's flags while it is bound (BindResidentBlocksRagged names the streams
-  // whose FIFO did not fire through silent.next; switching the rule off underneath it would advance every stream on every fired
-  // step while the key/value installs and the codebook lottery still skip the flagged ones -- ADVICE r05): refused in both directions
-  if (b->rb.on) return -1;
   if (!enable) {
     if (sr.on) { (void)sync_all(b); if (b->rw.ready) sr.on = false; else silent_release(b); }   // (the per-stream wrapper keeps the freeze machinery)
     return 0;
   }
   if (sr.on) return 0;
   if (b->tk.on) {   // tick mode (plain resident I/O): the flagged streams sit the next STEP out -- their step counters stand still and
-    if (b->hs.on || b->rb.on) return -1;   // travel with every step from then on (batch_tick.hip.h, ragged steps); with the 48 kHz wrapper around the ticks
-                                            // (BindResidentIO48k) that is the shell's rule on its blocks -- at two / four blocks per step on a stream's WHOLE step
+                    // travel with every step from then on (batch_tick.hip.h, ragged steps); with the 48 kHz wrapper around the ticks
+                    // (BindResidentIO48k) that is the shell's rule on its blocks -- at two / four blocks per step on a stream's WHOLE step
     sr.next.assign(b->B, 0);
     sr.any_next = false;
     sr.on = true;
     return 0;
   }
-  if (b->H != 1 || b->pipelined || b->tk.on || b->io_slots > 0) return -1;   // the in-order chain, one block per step
-  if (!sync_all(b)) return -2;
+  if (!sync_all(b)) return -2;   // the in-order chain, one block per step
   if (!freeze_prepare(b)) { silent_release(b); return -2; }
   sr.on = true;
   drop_graph(b);
@@ -112,8 +110,8 @@ static bool freeze_prepare(BeatriceBatch* b) {
 // streams whose NEXT 48 kHz block is silent by the shell's rule (flags[B], non-zero = silent); cleared by that block
 int BeatriceBatch_SetSilentStreams(BeatriceBatch* b, const unsigned char* flags) {
   if (!b || !b->ok) return -2;
-  if (!b->silent.on || !flags) return -1;
-  if ((b->H != 1 && !b->tk.on) || b->pipelined || (!b->tk.on && b->io_slots > 0) || (b->tk.on && (b->hs.on || b->rb.on))) return -1;   // (the rule's modes: EnableSilentBlockRule)
+  BATCH_GATE(b, Entry::SetSilentStreams);
+  if (!flags) return -1;
   b->silent.any_next = false;
   for (int s = 0; s < b->B; ++s) { b->silent.next[s] = flags[s] ? 1 : 0; b->silent.any_next = b->silent.any_next || flags[s]; }
   return 0;
@@ -123,30 +121,30 @@ int BeatriceBatch_SetSilentStreams(BeatriceBatch* b, const unsigned char* flags)
 // block lands in the same slot of d_out48 BeatriceBatch_TickStages() - 1 calls later (or after BeatriceBatch_Synchronize).
 // Same samples as the in-order BeatriceBatch_ConvertBlocks48kDevice.  NULL pointers unbind.
 int BeatriceBatch_BindResidentIO48k(BeatriceBatch* b, const float* d_in48, float* d_out48, int channels, int n_slots) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
+  const bool bind = d_in48 || d_out48;
+  if (bind) BATCH_GATE(b, Entry::BindResidentIO48k_bind);
   BeatriceBatch::Resident48& r = b->r48;
   if (r.on) {
     if (!sync_all(b)) return -2;
     const int rc = tick_enable(b, false);
     if (rc) return rc;
-    (void)BeatriceBatch_BindResidentIO(b, nullptr, nullptr, 0);
+    (void)bind_io(b, nullptr, nullptr, 0);
     if (r.d_in16) (void)hipFree(r.d_in16);
     if (r.d_out24) (void)hipFree(r.d_out24);
     r = BeatriceBatch::Resident48{};
   }
-  if (!d_in48 && !d_out48) return 0;
-  if (!d_in48 || !d_out48 || channels < 1 || channels > 2 || n_slots < b->tk.plan.count() + 1 || b->H > tick::kMaxHops || b->io_slots > 0 || b->pipelined ||
-      b->tk.on || b->hs.on || b->silent.on)   // (the silent-block rule is an in-order mode: switch it off first)
-    return -1;
+  if (!bind) return 0;
+  BATCH_GATE(b, Entry::BindResidentIO48k_bind);   // (again: the mode the batch is in now that it has left F)
+  if (!d_in48 || !d_out48 || channels < 1 || channels > 2 || n_slots < b->tk.plan.count() + 1) return -1;
   // (with H hops per step a slot holds H blocks per stream, [B][H][channels][480], and a call converts them all)
   bool ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_in16), sizeof(float) * n_slots * b->B * b->H * B_IN_HOP), "r48 in16") &&
             hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_out24), sizeof(float) * n_slots * b->B * b->H * B_OUT_HOP), "r48 out24") &&
             hip_ok(hipMemset(r.d_in16, 0, sizeof(float) * n_slots * b->B * b->H * B_IN_HOP), "r48 zero");
-  ok = ok && BeatriceBatch_BindResidentIO(b, r.d_in16, r.d_out24, n_slots) == 0 && tick_enable(b, true) == 0;
+  ok = ok && bind_io(b, r.d_in16, r.d_out24, n_slots) == 0 && tick_enable(b, true) == 0;
   if (!ok) {
     (void)tick_enable(b, false);
-    (void)BeatriceBatch_BindResidentIO(b, nullptr, nullptr, 0);
+    (void)bind_io(b, nullptr, nullptr, 0);
     if (r.d_in16) (void)hipFree(r.d_in16);
     if (r.d_out24) (void)hipFree(r.d_out24);
     r = BeatriceBatch::Resident48{};
@@ -156,16 +154,14 @@ int BeatriceBatch_BindResidentIO48k(BeatriceBatch* b, const float* d_in48, float
   return 0;
 }
 int BeatriceBatch_ConvertBlocks48kDevice(BeatriceBatch* b, const float* d_in, float* d_out, int channels) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (b->r48.on) return (!d_in && !d_out && channels == b->r48.channels) ? (tick_run(b, true) ? 0 : -2) : -1;
-  if (channels < 1 || channels > 2 || !d_in || !d_out || b->H != 1 || b->io_slots > 0 || b->pipelined || b->tk.on) return -1;  // per 10 ms block, in order
+  BATCH_ENTER(b, d_in || d_out ? Entry::ConvertBlocks48kDevice_ptrs : Entry::ConvertBlocks48kDevice_NULL);
+  if (!d_in && !d_out) return channels == b->r48.channels ? (tick_run(b, true) ? 0 : -2) : -1;   // (F: the next resident block)
+  if (channels < 1 || channels > 2 || !d_in || !d_out) return -1;  // per 10 ms block, in order
   return step_48k(b, d_in, d_out, channels) ? 0 : -2;
 }
 int BeatriceBatch_ConvertBlocks48k(BeatriceBatch* b, const float* in, float* out, int channels) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (channels < 1 || channels > 2 || !in || !out || b->H != 1 || b->io_slots > 0 || b->pipelined || b->tk.on) return -1;
+  BATCH_ENTER(b, Entry::ConvertBlocks48k);
+  if (channels < 1 || channels > 2 || !in || !out) return -1;
   const size_t n = (size_t)b->B * channels * 480;
   float* h_in = b->h_io48;
   float* h_out = b->h_io48 + (size_t)b->B * 2 * 480;
@@ -200,10 +196,7 @@ int BeatriceBatch_ConvertBlocks48k(BeatriceBatch* b, const float* in, float* out
 // ---- host-rate blocks with the whole wrapper on the device (wrapper.hip.h) -------------------------------------------
 namespace { constexpr int kInnerStride = wrapn::kMaxSamples + 64; }
 int BeatriceBatch_ConfigureWrapper(BeatriceBatch* b, double sample_rate) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (b->H != 1 && b->H != 2 && b->H != 4) return -1;   // (several hops per step: for BeatriceBatch_BindResidentBlocks, the wrapper around the ticks)
-  if (b->rb.on) return -1;                              // resident blocks are bound: the binding restarts the wrapper itself when it is made and released
+  BATCH_ENTER(b, Entry::ConfigureWrapper);   // (G, P: the binding restarts the wrapper itself when it is made and released; several hops per step: for BeatriceBatch_BindResidentBlocks)
   if (!sync_all(b)) return -2;
   if (!b->wrap.configure(sample_rate)) return -1;  // rate <= 0, or a ratio whose filter history exceeds the state block
   const int B = b->B;
@@ -231,15 +224,13 @@ int BeatriceBatch_ConfigureWrapper(BeatriceBatch* b, double sample_rate) {
 }
 // reference ProcessorCore2::SetInputGain / SetOutputGain (processor_core_2.cc:488-496): the target; the ramp follows at 2 dB/ms
 int BeatriceBatch_SetInputGain(BeatriceBatch* b, int stream, double db) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (stream < -1 || stream >= b->B || b->gain_in.empty()) return -1;
   for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? b->B : stream + 1); ++s) b->gain_in[s].target_db = db;
   return 0;
 }
 int BeatriceBatch_SetOutputGain(BeatriceBatch* b, int stream, double db) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
   if (stream < -1 || stream >= b->B || b->gain_out.empty()) return -1;
   for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? b->B : stream + 1); ++s) b->gain_out[s].target_db = db;
   return 0;
@@ -296,15 +287,14 @@ static int wrap_max_chunk(const BeatriceBatch* b) {  // host samples per launch 
 }
 // in / out: [B][channels][n] planar at the configured host rate; any n >= 1 (long blocks are processed in pieces)
 int BeatriceBatch_ProcessBlocksDevice(BeatriceBatch* b, const float* d_in, float* d_out, int channels, int n) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (b->rb.on) {
-    if (b->rb.ragged || d_in || d_out || channels != b->rb.channels || n != b->rb.n) return -1;
+  BATCH_ENTER(b, d_in || d_out ? Entry::ProcessBlocksDevice_ptrs : Entry::ProcessBlocksDevice_NULL);
+  if (!d_in && !d_out) {   // (G: the next resident block)
+    if (channels != b->rb.channels || n != b->rb.n) return -1;
     if (b->rb.dead) return -2;
     if (!rb_step(b)) { b->rb.dead = true; return -2; }   // (rb_step advances gain clocks, resampler phases and the FIFO before its checks: a failed call leaves the binding unusable, not silently skewed)
     return 0;
   }
-  if (!b->wrap.ready || channels < 1 || channels > 2 || !d_in || !d_out || n < 1 || b->H != 1 || b->io_slots > 0 || b->pipelined || b->tk.on) return -1;
+  if (channels < 1 || channels > 2 || !d_in || !d_out || n < 1) return -1;
   const int piece = wrap_max_chunk(b);
   if (n <= piece) return wrap_chunk(b, d_in, d_out, channels, n) ? 0 : -2;
   return -1;  // the planar layout [B][channels][n] cannot be cut without copies: callers pass blocks of at most `piece` samples
@@ -315,9 +305,8 @@ int BeatriceBatch_MaxWrapperBlock(const BeatriceBatch* b) { return b && b->ok &&
 // rates[B]: the host rate of every stream (streams of equal rate share their tap tables).  Restarts every stream's resampler
 // pair and FIFO as SetSampleRate does; the gains keep their state.  In-order mode, one hop per step.
 int BeatriceBatch_ConfigureWrapperRates(BeatriceBatch* b, const double* rates) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (!rates || b->H != 1 || b->pipelined || b->tk.on || b->io_slots > 0) return -1;
+  BATCH_ENTER(b, Entry::ConfigureWrapperRates);
+  if (!rates) return -1;
   if (!sync_all(b)) return -2;
   BeatriceBatch::RaggedWrap& r = b->rw;
   const int B = b->B;
@@ -404,10 +393,9 @@ static bool rag_plan(BeatriceBatch* b, int s, int n, wrapn::RagStream& q, wrapn:
 // THEIR 480-sample FIFO fills; a step runs for the streams that fire in it and leaves the others standing.
 int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* out, int channels, const int* n_samples, int apply_silent_rule) {
   using namespace wrapn;
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_ENTER(b, Entry::ProcessBlocksRagged);
   BeatriceBatch::RaggedWrap& r = b->rw;
-  if (!r.ready || !in || !out || !n_samples || channels < 1 || channels > 2 || b->H != 1 || b->io_slots > 0 || b->pipelined || b->tk.on) return -1;
+  if (!in || !out || !n_samples || channels < 1 || channels > 2) return -1;
   const int B = b->B;
   hipStream_t st = b->stream;
   size_t total = 0;
@@ -526,7 +514,7 @@ static int rb_unbind(BeatriceBatch* b) {
   if (!sync_all(b)) return -2;
   const int rc = tick_enable(b, false);
   if (rc) return rc;
-  (void)BeatriceBatch_BindResidentIO(b, nullptr, nullptr, 0);
+  (void)bind_io(b, nullptr, nullptr, 0);
   const bool ragged = r.ragged;
   rb_release(b);
   if (ragged) {
@@ -638,16 +626,16 @@ static bool rb_step(BeatriceBatch* b, const bool synthetic) {
 // same slot of d_out BeatriceBatch_ResidentBlocksDelay() calls later (or after BeatriceBatch_Synchronize).  Same samples as
 // the in-order BeatriceBatch_ProcessBlocksDevice.  n_slots > delay + 1.  NULL pointers unbind.
 int BeatriceBatch_BindResidentBlocks(BeatriceBatch* b, const float* d_in, float* d_out, int channels, int n, int n_slots) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
+  const bool bind = d_in || d_out;
+  if (bind) BATCH_GATE(b, Entry::BindResidentBlocks_bind);
   BeatriceBatch::ResidentBlocks& r = b->rb;
   if (r.on) { const int rc = rb_unbind(b); if (rc) return rc; }
-  if (!d_in && !d_out) return 0;
+  if (!bind) return 0;
+  BATCH_GATE(b, Entry::BindResidentBlocks_bind);   // (again: the mode the batch is in now that it has left G / P)
   const int stages = b->tk.plan.count();
   const int H = b->H;
-  if (!b->wrap.ready || !d_in || !d_out || channels < 1 || channels > 2 || n < 1 || n > wrap_max_chunk(b) || (H != 1 && H != 2 && H != 4) ||
-      b->io_slots > 0 || b->pipelined || b->tk.on || b->hs.on || b->r48.on || b->silent.on)
-    return -1;
+  if (!d_in || !d_out || channels < 1 || channels > 2 || n < 1 || n > wrap_max_chunk(b)) return -1;
   const int delay = rb_delay(b, n);
   if (delay < 0 || n_slots < delay + 2) return -1;
   // binding restarts the resampler pair and the FIFO (their in-order form keeps processed samples in the FIFO, this one does not)
@@ -672,10 +660,10 @@ int BeatriceBatch_BindResidentBlocks(BeatriceBatch* b, const float* d_in, float*
     for (int i = 0; i < r.ring && ok; ++i) ok = hip_ok(hipEventCreateWithFlags(&r.gain_ev[i], hipEventDisableTiming), "rb event");
     r.ev_recorded.assign(r.ring, 0);
   }
-  ok = ok && hip_ok(hipDeviceSynchronize(), "rb sync") && BeatriceBatch_BindResidentIO(b, r.d_in16, r.d_out24, r.io_slots) == 0 && tick_enable(b, true) == 0;
+  ok = ok && hip_ok(hipDeviceSynchronize(), "rb sync") && bind_io(b, r.d_in16, r.d_out24, r.io_slots) == 0 && tick_enable(b, true) == 0;
   if (!ok) {
     (void)tick_enable(b, false);
-    (void)BeatriceBatch_BindResidentIO(b, nullptr, nullptr, 0);
+    (void)bind_io(b, nullptr, nullptr, 0);
     rb_release(b);
     return -2;
   }
@@ -775,22 +763,21 @@ static int rbr_step(BeatriceBatch* b, const int* n_samples) {
   return ok ? 0 : -2;
 }
 int BeatriceBatch_ProcessBlocksRaggedDevice(BeatriceBatch* b, const int* n_samples) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (!b->rb.on || !b->rb.ragged || !n_samples) return -1;
+  BATCH_ENTER(b, Entry::ProcessBlocksRaggedDevice);
+  if (!n_samples) return -1;
   return rbr_step(b, n_samples);
 }
 // d_in / d_out: [n_slots][B][channels * max_samples]: stream s's block of a call, planar [channels][n_samples[s]], at the start of its cell
 int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, float* d_out, int channels, int max_samples, int n_slots) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_OPEN(b);
+  const bool bind = d_in || d_out;
+  if (bind) BATCH_GATE(b, Entry::BindResidentBlocksRagged_bind);
   BeatriceBatch::ResidentBlocks& r = b->rb;
   if (r.on) { const int rc = rb_unbind(b); if (rc) return rc; }
-  if (!d_in && !d_out) return 0;
+  if (!bind) return 0;
+  BATCH_GATE(b, Entry::BindResidentBlocksRagged_bind);   // (again: the mode the batch is in now that it has left G / P)
   const int stages = b->tk.plan.count();
-  if (!b->rw.ready || !d_in || !d_out || channels < 1 || channels > 2 || max_samples < 1 || n_slots < stages + 1 || b->H != 1 ||
-      b->io_slots > 0 || b->pipelined || b->tk.on || b->hs.on || b->r48.on || b->silent.on)
-    return -1;
+  if (!d_in || !d_out || channels < 1 || channels > 2 || max_samples < 1 || n_slots < stages + 1) return -1;
   const int B = b->B;
   // binding restarts every stream's resampler pair and FIFO (their in-order form keeps processed samples in the FIFO, this one does not)
   std::vector<double> rates(B);
@@ -823,10 +810,10 @@ int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, 
     for (int i = 0; i < r.ring && ok; ++i) ok = hip_ok(hipEventCreateWithFlags(&r.gain_ev[i], hipEventDisableTiming), "rb event");
     r.ev_recorded.assign(r.ring, 0);
   }
-  ok = ok && hip_ok(hipDeviceSynchronize(), "rb sync") && BeatriceBatch_BindResidentIO(b, r.d_in16, r.d_out24, r.io_slots) == 0 && tick_enable(b, true) == 0;
+  ok = ok && hip_ok(hipDeviceSynchronize(), "rb sync") && bind_io(b, r.d_in16, r.d_out24, r.io_slots) == 0 && tick_enable(b, true) == 0;
   if (!ok) {
     (void)tick_enable(b, false);
-    (void)BeatriceBatch_BindResidentIO(b, nullptr, nullptr, 0);
+    (void)bind_io(b, nullptr, nullptr, 0);
     rb_release(b);
     return -2;
   }
@@ -845,10 +832,8 @@ int BeatriceBatch_ResidentBlocksDelayFor(const BeatriceBatch* b, int n) { return
 // End of the material: every call made so far gets its output block as if silence had followed (several hops per step: the step still filling
 // is completed with hops of silence -- no caller slot is read or written for them), then the binding starts over as a new one does.
 int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
+  BATCH_ENTER(b, Entry::FlushResidentBlocks);
   BeatriceBatch::ResidentBlocks& r = b->rb;
-  if (!r.on) return -1;
   if (r.dead) return -2;
   if (!sync_all(b)) return -2;           // (one hop per step and clocks per stream: everything is out now)
   if (r.jobs.empty()) return 0;
@@ -875,9 +860,8 @@ int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b) {
 }
 int BeatriceBatch_ResidentBlocksOwed(const BeatriceBatch* b) { return b && b->ok && b->rb.on ? (int)b->rb.jobs.size() : -1; }
 int BeatriceBatch_ProcessBlocks(BeatriceBatch* b, const float* in, float* out, int channels, int n) {
-  const DeviceScope dev_(b ? b->device : -1);
-  if (!b || !b->ok) return -2;
-  if (!b->wrap.ready || channels < 1 || channels > 2 || !in || !out || n < 1 || n > wrap_max_chunk(b) || b->H != 1 || b->io_slots > 0 || b->pipelined || b->tk.on) return -1;
+  BATCH_ENTER(b, Entry::ProcessBlocks);
+  if (channels < 1 || channels > 2 || !in || !out || n < 1 || n > wrap_max_chunk(b)) return -1;
   const size_t cnt = (size_t)b->B * channels * n;
   float* h_in = b->h_wrap_io;
   float* h_out = b->h_wrap_io + (size_t)b->B * 2 * wrapn::kMaxSamples;

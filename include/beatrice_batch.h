@@ -97,6 +97,7 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  * flag -- tests/test_gpu_mode_matrix.py asks every "-" cell of this table between steps and compares the batch, bit for bit, with one that
  * never asked.  The "ok" cells are the -m gpu parity tests against the oracle.  Settings (BeatriceBatch_Set*, ResetStream, Morph*,
  * SetInputGain / SetOutputGain once a wrapper is configured) work in every mode and apply to the step / call that follows them.
+ * The library decides on this table as code: beatrice-vst_amd/csrc/batch_modes.h, held against the test's matrix by tests/test_cpu_mode_table.py.
  *
  *   mode (how it is entered)                                        H           its entry point per step / call
  *   A  in order            (a new batch)                            1 2 4 8     ConvertFrames, ConvertFramesDevice
@@ -123,20 +124,20 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *   ProcessBlocksRagged                  ok (2)   -     -     -        -     -        -     -     - (2)
  *   ProcessBlocksRaggedDevice            -        -     -     -        -     -        -     ok    -
  *   StreamFrames / StreamFlush           -        -     -     -        ok    -        -     -     -
- *   EnableSilentBlockRule(1)             ok, H=1  -     -     ok (6)   -     ok (6)   -     -     ok
+ *   EnableSilentBlockRule(1)             ok, H=1  -     - (7) ok (6)   -     ok (6)   -     -     ok
  *   EnableSilentBlockRule(0)             ok       ok    ok    ok       ok    ok       -     -     ok
  *   SetSilentStreams                     - (3)    -     -     - (3)    -     - (3)    -     -     ok
- *   EnablePipelining(n)                  ok       ok    ok    -        -     -        -     -     - (n >= 1)
- *   EnableTickPipeline(1)                -        -     ok(4) ok       -     -        -     -     -
+ *   EnablePipelining(n)                  ok       ok    ok(7) -        -     -        -     -     - (n >= 1)
+ *   EnableTickPipeline(1)                -        -     ok(4,7) ok(7)  -     -        -     -     -
  *   EnableTickPipeline(0)                ok       ok    ok    ok       -     -        -     -     ok
- *   EnableHostStreaming(1)               ok       -     -     -        ok    -        -     -     -
- *   BindResidentIO (bind)                ok       ok    ok    -        -     -        -     -     -
+ *   EnableHostStreaming(1)               ok (8)   -     -     -        ok    -        -     -     -
+ *   BindResidentIO (bind)                ok       ok    ok(7) -        -     -        -     -     -
  *   BindResidentIO (NULL, NULL)          ok       ok    ok    -        -     -        -     -     ok
- *   BindResidentIO48k (bind)             ok       -     -     -        -     ok (5)   -     -     -
+ *   BindResidentIO48k (bind)             ok (8)   -     -     -        -     ok (5)   -     -     -
  *   BindResidentBlocks (bind)            ok (1)   -     -     -        -     -        ok(5) ok(5) -
  *   BindResidentBlocksRagged (bind)      ok (2)   -     -     -        -     -        ok(5) ok(5) -
  *   Bind...(NULL, NULL) of F / G / P     ok       ok    ok    ok       ok    leaves F leaves G / P      ok
- *   ConfigureWrapper                     ok       ok    ok    ok       ok    ok       -     -     ok
+ *   ConfigureWrapper (8)                 ok       ok    ok    ok       ok    ok       -     -     ok
  *   ConfigureWrapperRates                ok, H=1  -     -     -        -     -        -     -     ok
  *   ProfileKernels                       ok       ok    ok    -        -     -        -     -     ok
  *   TimeSteps                            ok       ok    ok    ok       -     -        -     -     ok
@@ -148,7 +149,10 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *   (4) with more resident slots than BeatriceBatch_TickStages() and at most 4096 of them, B <= 4096, H = 1 / 2 / 4.
  *   (6) at H = 2 / 4 a flagged stream sits a WHOLE step (its H hops / its H 48 kHz blocks) out: the caller flags a stream whose blocks of the step are ALL silent.  One
  *       silent block among sounding ones of the same step cannot be skipped there (it is converted as the sounding ones are) -- the shell's per-block rule needs one hop per step.
- *   (5) a bind call on a batch that is already in F / G / P first LEAVES that mode (drains, restarts the wrapper), then binds anew.
+ *   (5) a bind call on a batch that is already in F / G / P first LEAVES that mode (drains, restarts the wrapper), then binds anew: by the A column, as on any batch.
+ *   (7) a rule enabled in D / F stays on when the batch leaves tick mode after BeatriceBatch_ConfigureWrapperRates (which keeps the rule's buffers): while it is on,
+ *       these calls are refused in C (and a second EnableTickPipeline(1) in D), and EnableSilentBlockRule(1) returns 0.  EnableSilentBlockRule(0) clears it.
+ *   (8) H = 1 / 2 / 4: -1 on a batch of eight hops per step.
  *
  * Environment variables the library reads: BEATRICE_HIP_DEBUG (print HIP errors to stderr), BEATRICE_HIP_CUMASK ("lo-hi;lo-hi;..": CU masks
  * of the stage-pipelining streams), BEATRICE_HIP_HOP_GRAPH (the 1-stream calls replayed as hipGraphs), BEATRICE_HIP_NO_SPECULATION (no pitch hop beside
