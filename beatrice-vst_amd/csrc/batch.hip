@@ -13,7 +13,6 @@
 #include <cstring>
 #include <limits>
 #include <memory>
-#include <deque>
 #include <numeric>
 #include <random>
 #include <string>
@@ -63,20 +62,20 @@ struct MorphSlot {
 template <class T>
 struct Mirror {
   T* h = nullptr;  // the buffer being edited
-  T* d = nullptr;
+  DevBuf<T> d;
   size_t n = 0;
-  T* buf[2] = {nullptr, nullptr};
-  hipEvent_t sent[2] = {nullptr, nullptr};
+  PinnedBuf<T> buf[2];
+  Event sent[2];
   bool pending[2] = {false, false};
   int cur = 0;
-  bool alloc_host(size_t n_) {
-    n = n_;
-    for (int i = 0; i < 2; ++i) {
-      BHIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&buf[i]), sizeof(T) * n, hipHostMallocDefault));
-      std::memset(buf[i], 0, sizeof(T) * n);
-      BHIP_TRY(hipEventCreateWithFlags(&sent[i], hipEventDisableTiming));
-    }
-    h = buf[0];
+  // n_host elements per pinned buffer (zeroed); the device array has n_dev, zeroed if asked
+  bool alloc(size_t n_host, size_t n_dev, const char* what, bool zero_dev) {
+    Mirror m;
+    m.n = n_host;
+    for (int i = 0; i < 2; ++i) if (!m.buf[i].alloc(n_host, what) || !m.sent[i].create(what)) return false;
+    if (!m.d.alloc(n_dev, what, zero_dev)) return false;
+    m.h = m.buf[0];
+    *this = std::move(m);
     return true;
   }
   // sends [off, off + len) of the edited buffer to dst (nullptr: d + off) for each part, then flips
@@ -95,15 +94,6 @@ struct Mirror {
     h = buf[cur];
     return true;
   }
-  void release() {
-    for (int i = 0; i < 2; ++i) {
-      if (pending[i]) (void)hipEventSynchronize(sent[i]);
-      if (buf[i]) (void)hipHostFree(buf[i]);
-      if (sent[i]) (void)hipEventDestroy(sent[i]);
-      buf[i] = nullptr; sent[i] = nullptr; pending[i] = false;
-    }
-    h = nullptr;
-  }
 };
 
 }  // namespace
@@ -117,14 +107,14 @@ struct BeatriceBatch {
   int device = -1;  // the GPU of the model objects the batch was created from; every entry point runs with it current (DeviceScope)
   int H = 1;  // hops per step (block mode when > 1)
   bool ok = false;
-  hipStream_t stream = nullptr;
-  bool owns_stream = false;
+  hipStream_t stream = nullptr;  // stream_own, or the caller's (BeatriceBatch_SetStream)
+  Stream stream_own;
   PhoneState phone;
   PitchState pitch;
   WaveState wave;
-  float* d_in = nullptr;  // [B][H*160], shared by phone and pitch
+  DevBuf<float> d_in;  // [B][H*160], shared by phone and pitch
   // speaker tables on device
-  float *d_cb_raw = nullptr, *d_cbT = nullptr, *d_cnorm = nullptr, *d_add_raw = nullptr, *d_frm_raw = nullptr, *d_kv_raw = nullptr;
+  DevBuf<float> d_cb_raw, d_cbT, d_cnorm, d_add_raw, d_frm_raw, d_kv_raw;
   // per-stream settings
   std::vector<StreamCfg> cfg;
   std::vector<MorphSlot> morph;  // [max_speakers]
@@ -151,7 +141,7 @@ struct BeatriceBatch {
   bool vq_dirty = true;   // a VQ setting changed since the k-NN launch was last (de)selected
   bool inflight = false;  // device-variant steps have been enqueued since the last synchronisation
   // staging for the host variant
-  float *h_in = nullptr, *h_out = nullptr;
+  PinnedBuf<float> h_in, h_out;
   // One step = a chain of stages: stage 0 the front end (content encoder + pitch estimator + conditioning mix),
   // stages 1.. consecutive parts of the waveform generator (WavePart).  Each stage is its own launch (graph).
   // With pipelining off all stages go to `stream`, in order.  With a pipeline depth of n = 2..4 there are n
@@ -170,17 +160,17 @@ struct BeatriceBatch {
   int n_stages = 2;      // stages of the current plan (2 when pipelining is off: front end, whole generator)
   bool pipelined = false;
   WavePart part[kMaxStages] = {};                 // [s], s >= 1
-  hipStream_t stage_stream_own[kMaxStages] = {};  // [s], s >= 1; stage 0 runs on `stream`
-  hipEvent_t ev_done[kMaxStages][kSlots] = {};    // stage s of step t enqueued/done, at [t & 3]
+  Stream stage_stream_own[kMaxStages];            // [s], s >= 1; stage 0 runs on `stream`
+  Event ev_done[kMaxStages][kSlots];              // stage s of step t enqueued/done, at [t & 3]
   long long steps_enqueued = 0;
   int hop_host = 0;     // mirror of the device step counter (same increments, same wrap)
   int last_parity = 0;  // slot (step counter mod 3) of the last enqueued step's phone vectors
-  int* d_hop_wave = nullptr;  // int[4][2]: {counter, I/O slot} of step t at [t & 3], for the waveform generator's stages
+  DevBuf<int> d_hop_wave;     // int[4][2]: {counter, I/O slot} of step t at [t & 3], for the waveform generator's stages
   bool use_graph = true;
   hipGraph_t graph[kMaxStages][kSlots] = {};      // pipelined: stage 0 uses [0][0] only; in order: [0][slot] holds the whole step
   hipGraphExec_t exec[kMaxStages][kSlots] = {};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int* d_hop_next = nullptr;  // {step counter, resident-I/O slot}, double-buffered: first kernels read it, the last one writes it
+  Event ev0, ev1;             // (timing enabled)
+  DevBuf<int> d_hop_next;     // {step counter, resident-I/O slot}, double-buffered: first kernels read it, the last one writes it
   float* own_d_out = nullptr; // the waveform module's output buffer while a resident output buffer is bound
   int io_slots = 0;           // > 0: resident I/O bound (BeatriceBatch_BindResidentIO)
   bool io_mapped = false;     // BeatriceBatch_ConvertFrames: the chain reads the pinned input mirror and writes the pinned output mirror itself
@@ -194,11 +184,11 @@ struct BeatriceBatch {
   struct HostStream {
     bool on = false;
     int n_slots = 0;
-    float *d_in = nullptr, *d_out = nullptr;   // [n_slots][B][160], [n_slots][B][240]: the resident I/O the ticks use
-    float *h_in = nullptr, *h_out = nullptr;   // pinned mirrors
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    std::vector<hipEvent_t> ev_in, ev_out;     // per slot: upload done / download done
-    std::vector<hipEvent_t> ev_tick;           // ring over ticks: tick launched (recorded on the batch's stream)
+    DevBuf<float> d_in, d_out;                 // [n_slots][B][160], [n_slots][B][240]: the resident I/O the ticks use
+    PinnedBuf<float> h_in, h_out;              // pinned mirrors
+    Stream s_in, s_out;
+    std::vector<Event> ev_in, ev_out;          // per slot: upload done / download done
+    std::vector<Event> ev_tick;                // ring over ticks: tick launched (recorded on the batch's stream)
     struct Pending { long long step; int slot; long long done_tick; bool fetched; };
     std::deque<Pending> pending;               // steps fed and not yet handed back, oldest first
     long long fed = 0;
@@ -209,23 +199,25 @@ struct BeatriceBatch {
   // any-rate device wrapper (wrapper.hip.h): the reference host's gains, resampler pair and 480-sample FIFO for all streams
   wrapn::WrapPlan wrap;
   std::vector<wrapn::GainClock> gain_in, gain_out;  // [B]
-  wrapn::StreamState* d_wrap = nullptr;             // [B]
-  float *d_wrap_taps = nullptr, *d_wrap_inner = nullptr, *d_wrap_io = nullptr, *h_wrap_io = nullptr;  // taps: down | up; inner [B][kInnerStride]
+  DevBuf<wrapn::StreamState> d_wrap;                // [B]
+  DevBuf<float> d_wrap_taps, d_wrap_inner, d_wrap_io;   // taps: down | up; inner [B][kInnerStride]
+  PinnedBuf<float> h_wrap_io;
   Mirror<wrapn::GainSeg> wrap_gains;                // [2][B]: input | output segments of the current call
   bool wrap_gains_constant = false;                 // the device copy holds constant segments that are still right
   // 48 kHz device wrapper (configs[4])
-  Wrap48State* d_w48 = nullptr;
+  DevBuf<Wrap48State> d_w48;
   // the same wrapper around the TICK pipeline (BeatriceBatch_BindResidentIO48k): resident 48 kHz slots, own 16 / 24 kHz slots between
   struct Resident48 {
     bool on = false;
     int channels = 0, n_slots = 0;
     const float* d_in48 = nullptr;   // [n_slots][B][channels][480]
     float* d_out48 = nullptr;        // [n_slots][B][channels][480]
-    float *d_in16 = nullptr, *d_out24 = nullptr;  // [n_slots][B][160], [n_slots][B][240]: the resident I/O of the ticks
+    DevBuf<float> d_in16, d_out24;                // [n_slots][B][160], [n_slots][B][240]: the resident I/O of the ticks
     int deferred_slot = -1;                       // step completed by the last tick, its 48 kHz block not yet produced
     long long deferred_step = -1;                 // ... and which step that was (its per-stream counters name its silent streams)
   } r48;
-  float *d_coef_down = nullptr, *d_coef_up = nullptr, *d_io48 = nullptr, *h_io48 = nullptr;  // io: in [B][2][480] | out [B][2][480]
+  DevBuf<float> d_coef_down, d_coef_up, d_io48;   // io: in [B][2][480] | out [B][2][480]
+  PinnedBuf<float> h_io48;
   // The shell's silent-block rule per stream (BeatriceBatch_EnableSilentBlockRule; kernels_misc.hip.h freeze_*): streams
   // flagged for the next 48 kHz block stand still -- model state, wrapper state, key/value installs, codebook lottery
   struct SilentRule {
@@ -234,13 +226,11 @@ struct BeatriceBatch {
     bool any_next = false;
     bool in_block_step = false;         // the step being enqueued belongs to a 48 kHz block (only those honour `next`)
     static constexpr int kDepth = 4;
-    unsigned char *d_flags = nullptr, *h_flags = nullptr;   // [kDepth][B]: a step's flags on the device / their pinned staging
-    hipEvent_t flag_ev[kDepth] = {};                        // slot's upload AND the step that reads the device copy are done
-    bool flag_pending[kDepth] = {};
-    FreezeRing* d_rings = nullptr;
+    StagedRing<unsigned char> flags;    // [kDepth][B]: a step's flags, pinned staging and device copy; an entry's event: its upload AND the step that reads the device copy are done
+    DevBuf<FreezeRing> d_rings;
     int n_rings = 0;
-    float* d_keep = nullptr;            // copies of the single-slot rings, all streams
-    int* d_keep_prev_q = nullptr;       // [B]
+    DevBuf<float> d_keep;               // copies of the single-slot rings, all streams
+    DevBuf<int> d_keep_prev_q;          // [B]
     long long steps = 0;
   } silent;
   // The any-rate wrapper with clocks PER STREAM (BeatriceBatch_ConfigureWrapperRates / ProcessBlocksRagged; wrapper.hip.h
@@ -254,13 +244,11 @@ struct BeatriceBatch {
     std::vector<Clock> clk_undo;                   // what ProcessBlocksRagged restores when a call is refused half-way through its plan
     std::vector<wrapn::GainClock> gain_undo_in, gain_undo_out;
     std::vector<int> taps_down_off, taps_up_off;   // per class: float offsets into d_taps
-    float* d_taps = nullptr;
+    DevBuf<float> d_taps;
     static constexpr int kStage = 4;
-    wrapn::RagStream *d_rs = nullptr, *h_rs = nullptr;   // [kStage][B]: a call's per-stream records, pinned staging and device copy
-    hipEvent_t ev[kStage] = {};
-    bool pending[kStage] = {};
+    StagedRing<wrapn::RagStream> rs;               // [kStage][B]: a call's per-stream records, pinned staging and device copy
     long long calls = 0;
-    unsigned char* d_frozen = nullptr;             // [kMaxChunks][B]: per FIFO chunk, the streams that do not fire a hop in it
+    DevBuf<unsigned char> d_frozen;                // [kMaxChunks][B]: per FIFO chunk, the streams that do not fire a hop in it
   } rw;
   // The any-rate wrapper around the tick pipeline (BeatriceBatch_BindResidentBlocks): host-rate blocks resident on the device,
   // the input half of the chain in front of the ticks, the output half `delay` calls later (wrapper.hip.h wrap_post_kernel)
@@ -271,13 +259,12 @@ struct BeatriceBatch {
     int channels = 0, n = 0, n_slots = 0, io_slots = 0, delay = 0, ring = 0;
     const float* d_in = nullptr;   // [n_slots][B][channels][n]
     float* d_out = nullptr;        // [n_slots][B][channels][n]
-    float *d_in16 = nullptr, *d_out24 = nullptr;   // [io_slots][B][H][160], [io_slots][B][H][240]: the resident I/O of the ticks
-    wrapn::GainSeg* h_gains = nullptr;                       // [ring][2][B] pinned: a call's input | output segments, read by the kernels in place
-    hipEvent_t* gain_ev = nullptr;                           // [ring]: the output half that read ring entry i has run
+    DevBuf<float> d_in16, d_out24;                 // [io_slots][B][H][160], [io_slots][B][H][240]: the resident I/O of the ticks
+    StagedRing<wrapn::GainSeg> gains;                        // [ring][2][B]: a call's input | output segments, read by the kernels in place; an entry's
+                                                             // event: the output half that read it has run (it guards h_rs[entry] of the per-stream form too)
     long long calls = 0, t48 = 0;                            // calls so far; 48 kHz samples fed so far
     long long hops_fired = 0;                                // model hops the FIFO has fired; hop k = hop k % H of step k / H
     long long hops_done = 0;                                 // hops of the steps fed by the end of the previous call
-    std::vector<char> ev_recorded;                           // [ring] gain_ev[i] marks the output half that read ring entry i last
     int H = 1;                                               // hops per step of the batch
     long long hops_fed() const { return hops_fired / H * H; }   // ... of which the hops of full steps are inside (or through) the ticks
     struct Job {
@@ -285,14 +272,14 @@ struct BeatriceBatch {
       long long last_hop() const { return (t0 + dout.n_in - 1) / wrapn::kBlock - 1; }   // the newest model hop its samples come from (wrap_post_kernel)
     };
     std::deque<Job> jobs;                                    // calls whose output half is still to run, oldest first
-    float* d_zero = nullptr;                                 // [B][channels][n] zeros: the input of the calls BeatriceBatch_FlushResidentBlocks makes up
+    DevBuf<float> d_zero;                                    // [B][channels][n] zeros: the input of the calls BeatriceBatch_FlushResidentBlocks makes up
     // the form with clocks PER STREAM (BeatriceBatch_BindResidentBlocksRagged; the rates, clocks and tap tables are `rw`'s): a slot
     // holds one cell of channels x max_samples floats per stream; a call's per-stream records stay on the device until its output
     // half has run; slot_map[b][g mod map_ring] = the resident slot of the step that stream b's hop g rode in
     bool ragged = false;
     int max_samples = 0, cell = 0, map_ring = 0;
-    wrapn::RagStream* h_rs = nullptr;                        // [ring][B] pinned, read by the kernels in place
-    int* d_map = nullptr;                                    // [B][map_ring]
+    PinnedBuf<wrapn::RagStream> h_rs;                        // [ring][B], read by the kernels in place
+    DevBuf<int> d_map;                                       // [B][map_ring]
     std::vector<long long> t48_s;                            // [B] 48 kHz samples of the stream fed so far
     std::vector<int> hops_s;                                 // [B] model hops the stream has fired
   } rb;
@@ -300,13 +287,12 @@ struct BeatriceBatch {
 
 namespace {
 
-// Waits for the steps enqueued so far (needed before the graph or a speaker table they use is replaced;
-// the pinned setting mirrors are double-buffered and do not need it).
-hipStream_t stage_stream(const BeatriceBatch* b, int s) { return b->pipelined && s > 0 ? b->stage_stream_own[s] : b->stream; }
+hipStream_t stage_stream(const BeatriceBatch* b, int s) { return b->pipelined && s > 0 ? b->stage_stream_own[s].get() : b->stream; }
 hipStream_t wave_stream(const BeatriceBatch* b) { return stage_stream(b, b->n_stages - 1); }  // where a step's output appears
 bool tick_drain(BeatriceBatch* b);
-void host_stream_free(BeatriceBatch* b);
 void drop_graph(BeatriceBatch* b);
+// Waits for the steps enqueued so far (needed before the graph or a speaker table they use is replaced;
+// the pinned setting mirrors are double-buffered and do not need it).
 bool sync_all(BeatriceBatch* b) {
   bool ok = !b->tk.on || tick_drain(b);  // steps still inside the tick pipeline come out first
   ok = hip_ok(hipStreamSynchronize(b->stream), "sync") && ok;
@@ -333,7 +319,8 @@ bool sync_all(BeatriceBatch* b) {
 }
 // Experiment switch: BEATRICE_HIP_CUMASK="lo-hi;lo-hi;..." gives the stream of stage 0, 1, ... a CU mask (CU index
 // ranges), so that concurrently running stages do not land on the same CUs.
-bool make_stage_stream(hipStream_t* st, int stage) {
+bool make_stage_stream(Stream& st, int stage) {
+  hipStream_t s = nullptr;
   const char* spec = std::getenv("BEATRICE_HIP_CUMASK");
   if (spec) {
     std::string sp(spec);
@@ -344,11 +331,15 @@ bool make_stage_stream(hipStream_t* st, int stage) {
       if (std::sscanf(sp.c_str() + pos, "%d-%d", &lo, &hi) == 2 && lo >= 0 && hi >= lo && hi < 512) {
         uint32_t mask[16] = {};
         for (int c = lo; c <= hi; ++c) mask[c >> 5] |= 1u << (c & 31);
-        return hip_ok(hipExtStreamCreateWithCUMask(st, 16, mask), "cu mask stream");
+        if (!hip_ok(hipExtStreamCreateWithCUMask(&s, 16, mask), "cu mask stream")) return false;
+        st.adopt(s);
+        return true;
       }
     }
   }
-  return make_stream(st);
+  if (!make_stream(&s)) return false;
+  st.adopt(s);
+  return true;
 }
 
 // stage plans by pipeline depth (waveform parts: 1 input mix, 2..5 blocks, 6 upsampler GEMMs, 7 tail); the cuts
@@ -704,9 +695,7 @@ int model_blob(Model* m, int allocate, void** d_ptr, size_t* n_bytes) {
   const DeviceScope dev_(m->device);
   const size_t n = Weights::n_floats();
   if (allocate && !m->loaded && m->blob.n_floats != n) {
-    m->blob.release();
-    if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&m->blob.d), n * sizeof(float)), "blob alloc")) return -2;
-    m->blob.n_floats = n;
+    if (!m->blob.alloc(n)) return -2;
   }
   if (!m->blob.d || m->blob.n_floats != n) return -1;
   *d_ptr = m->blob.d;
@@ -726,8 +715,6 @@ int model_ready(Model* m) {
 
 extern "C" {
 static bool rb_step(BeatriceBatch* b, bool synthetic = false);
-static void rb_release(BeatriceBatch* b);
-static void silent_release(BeatriceBatch* b);
 
 // ---- memory loaders ---------------------------------------------------------------------------
 #define BHIP_MEMORY_LOADER(Name, Obj, KIND, Weights)                                                        \
@@ -797,10 +784,9 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
   b->phone_m = phone; b->pitch_m = pitch; b->wave_m = wave; b->embed_m = embed;
   b->B = n_streams; b->max_speakers = max_speakers; b->H = hops_per_step;
   const int B = n_streams, S = max_speakers, H = hops_per_step;
-  bool ok = make_stage_stream(&b->stream, 0);
-  b->owns_stream = ok;
-  ok = ok && hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_in), sizeof(float) * B * H * B_IN_HOP), "d_in") &&
-       hip_ok(hipMemset(b->d_in, 0, sizeof(float) * B * H * B_IN_HOP), "d_in0");
+  bool ok = make_stage_stream(b->stream_own, 0);
+  b->stream = b->stream_own;
+  ok = ok && b->d_in.alloc((size_t)B * H * B_IN_HOP, "d_in");
   // the front end's outputs (phone vector, conditioning mix) have three step slots: see `pipelined`
   const bool slack = H <= tick::kMaxHops;  // rings sized so that every layer can be its own pipeline stage (tick.hip.h)
   ok = ok && b->phone.create(B, H, b->d_in, 3, slack) && b->pitch.create(B, H, b->d_in, true, slack) &&
@@ -810,30 +796,20 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
   // first kernels (phone.f1, pitch.fft) read the pair {counter, I/O slot} from d_hop_next; phone.f1 publishes
   // it to phone.d_hop for the rest of the front end and to d_hop_wave[counter & 1] for the waveform generator
   // (which may lag one step behind); the front end's last body (wave.cond) stores the next pair to d_hop_next.
-  ok = ok && hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_hop_next), 2 * sizeof(int)), "hop_next") &&
-       hip_ok(hipMemset(b->d_hop_next, 0, 2 * sizeof(int)), "hop_next0") &&
-       hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_hop_wave), 8 * sizeof(int)), "hop_wave") &&
-       hip_ok(hipMemset(b->d_hop_wave, 0, 8 * sizeof(int)), "hop_wave0");
+  ok = ok && b->d_hop_next.alloc(2, "hop_next") && b->d_hop_wave.alloc(8, "hop_wave");
   b->pitch.hop = b->phone.d_hop; b->wave.hop = b->d_hop_wave;
   b->phone.hop_in = b->d_hop_next; b->pitch.hop_in = b->d_hop_next;
   b->phone.hop_publish = b->phone.d_hop; b->phone.hop_publish_wave = b->d_hop_wave;
   b->wave.front_hop = b->phone.d_hop; b->wave.front_next_out = b->d_hop_next;
   b->phone.advance_hop = false; b->pitch.advance_hop = false; b->wave.advance_hop = false;
   for (int s = 0; s < BeatriceBatch::kMaxStages && ok; ++s) {  // (stage streams are created when a pipeline depth asks for them)
-    for (int k = 0; k < BeatriceBatch::kSlots && ok; ++k) ok = hip_ok(hipEventCreateWithFlags(&b->ev_done[s][k], hipEventDisableTiming), "ev");
+    for (int k = 0; k < BeatriceBatch::kSlots && ok; ++k) ok = b->ev_done[s][k].create("ev");
   }
   set_plan(b, 1);
   const size_t cbf = (size_t)S * B_CODEBOOK * B_PHONE_CH, kvf = (size_t)S * B_KV_LEN * B_KV_CH;
-  ok = ok && hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_cb_raw), sizeof(float) * cbf), "cb") &&
-       hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_cbT), sizeof(float) * cbf), "cbT") &&
-       hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_cnorm), sizeof(float) * S * B_CODEBOOK), "cnorm") &&
-       hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_add_raw), sizeof(float) * S * B_HID), "add") &&
-       hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_frm_raw), sizeof(float) * 9 * B_HID), "frm") &&
-       hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_kv_raw), sizeof(float) * kvf), "kv");
-  ok = ok && hip_ok(hipMemset(b->d_cbT, 0, sizeof(float) * cbf), "cbT0") && hip_ok(hipMemset(b->d_cnorm, 0, sizeof(float) * S * B_CODEBOOK), "cn0") &&
-       // entries the caller never fills (a morph entry's codebook, speakers added later) project to zeros, not to garbage
-       hip_ok(hipMemset(b->d_cb_raw, 0, sizeof(float) * cbf), "cb0") && hip_ok(hipMemset(b->d_add_raw, 0, sizeof(float) * S * B_HID), "add0") &&
-       hip_ok(hipMemset(b->d_frm_raw, 0, sizeof(float) * 9 * B_HID), "frm0") && hip_ok(hipMemset(b->d_kv_raw, 0, sizeof(float) * kvf), "kv0");
+  // (zeroed: entries the caller never fills -- a morph entry's codebook, speakers added later -- project to zeros, not to garbage)
+  ok = ok && b->d_cb_raw.alloc(cbf, "cb") && b->d_cbT.alloc(cbf, "cbT") && b->d_cnorm.alloc((size_t)S * B_CODEBOOK, "cnorm") &&
+       b->d_add_raw.alloc((size_t)S * B_HID, "add") && b->d_frm_raw.alloc((size_t)9 * B_HID, "frm") && b->d_kv_raw.alloc(kvf, "kv");
   b->cfg.assign(B, StreamCfg());
   b->morph.assign(S, MorphSlot());
   b->lottery.resize(B);
@@ -855,9 +831,7 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
     b->off.wave_bytes = o - b->off.front_bytes;
   }
   const size_t dev_bytes = b->off.front_bytes + BeatriceBatch::kSlots * b->off.wave_bytes;
-  ok = ok && b->settings.alloc_host(b->off.front_bytes + b->off.wave_bytes) &&
-       hip_ok(hipMalloc(reinterpret_cast<void**>(&b->settings.d), dev_bytes), "settings") &&
-       hip_ok(hipMemset(b->settings.d, 0, dev_bytes), "settings0");
+  ok = ok && b->settings.alloc(b->off.front_bytes + b->off.wave_bytes, dev_bytes, "settings", true);
   if (ok) {  // the kernels read the block instead of the modules' own arrays
     void** keep = b->module_owned;
     auto swap_in = [&keep](auto*& member, auto* view) { *keep++ = (void*)member; member = view; };
@@ -874,9 +848,8 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
       swap_in(b->wave.d_tile_slot[blk], b->dev_view<int>(b->off.tile_slot[blk]));
     }
   }
-  ok = ok && hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_in), sizeof(float) * B * H * B_IN_HOP, hipHostMallocDefault), "h_in") &&
-       hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_out), sizeof(float) * B * H * B_OUT_HOP, hipHostMallocDefault), "h_out") &&
-       hip_ok(hipEventCreate(&b->ev0), "ev0") && hip_ok(hipEventCreate(&b->ev1), "ev1");
+  ok = ok && b->h_in.alloc((size_t)B * H * B_IN_HOP, "h_in") && b->h_out.alloc((size_t)B * H * B_OUT_HOP, "h_out") &&
+       b->ev0.create("ev0", true) && b->ev1.create("ev1", true);
   {  // 48 kHz wrapper: 33-entry Hann-windowed sinc tables of the ratio-1/1 resampler pair
     //   (reference resample.h:209-230 with cutoffs 0.99*16000/48000 in, 0.99*24000/48000 out, :412-417)
     float cd[33], cu[33];
@@ -888,14 +861,10 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
       cd[i] = static_cast<float>(cut_d * sinc(x * cut_d) * hann);
       cu[i] = static_cast<float>(cut_u * sinc(x * cut_u) * hann);
     }
-    ok = ok && hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_w48), sizeof(Wrap48State) * B), "w48") &&
-         hip_ok(hipMemset(b->d_w48, 0, sizeof(Wrap48State) * B), "w48 0") &&
-         hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_coef_down), sizeof(cd)), "cd") &&
-         hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_coef_up), sizeof(cu)), "cu") &&
+    ok = ok && b->d_w48.alloc(B, "w48") && b->d_coef_down.alloc(33, "cd", false) && b->d_coef_up.alloc(33, "cu", false) &&
          hip_ok(hipMemcpy(b->d_coef_down, cd, sizeof(cd), hipMemcpyHostToDevice), "cd up") &&
          hip_ok(hipMemcpy(b->d_coef_up, cu, sizeof(cu), hipMemcpyHostToDevice), "cu up") &&
-         hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_io48), sizeof(float) * B * 4 * 480), "io48") &&
-         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_io48), sizeof(float) * B * 4 * 480, hipHostMallocDefault), "hio48");
+         b->d_io48.alloc((size_t)B * 4 * 480, "io48", false) && b->h_io48.alloc((size_t)B * 4 * 480, "hio48");
   }
   ok = ok && hip_ok(hipDeviceSynchronize(), "create sync");  // NULL-stream memsets vs the non-blocking stream
   b->ok = ok;
@@ -912,23 +881,6 @@ void BeatriceBatch_Destroy(BeatriceBatch* b) {
   if (!b) return;
   if (b->stream) (void)sync_all(b);
   drop_graph(b);
-  if (b->tk.d_hopv) (void)hipFree(b->tk.d_hopv);
-  if (b->tk.h_hopv) (void)hipHostFree(b->tk.h_hopv);
-  for (hipEvent_t e : b->tk.hv_ev) if (e) (void)hipEventDestroy(e);
-  { void* wr[] = {b->d_wrap, b->d_wrap_taps, b->d_wrap_inner, b->d_wrap_io, b->wrap_gains.d, b->rw.d_taps, b->rw.d_rs, b->rw.d_frozen}; for (void* p : wr) if (p) (void)hipFree(p); }
-  if (b->rw.h_rs) (void)hipHostFree(b->rw.h_rs);
-  for (hipEvent_t e : b->rw.ev) if (e) (void)hipEventDestroy(e);
-  if (b->h_wrap_io) (void)hipHostFree(b->h_wrap_io);
-  b->wrap_gains.release();
-  { void* tk[] = {b->tk.d_table, b->tk.d_table_sparse, b->tk.d_snap, b->tk.d_trace, b->tk.d_link_q, b->tk.d_link_p, b->tk.d_desc, b->tk.d_desc_sparse, b->tk.d_desc_plain, b->tk.d_desc_ranges, b->tk.d_ring_table, b->tk.d_shift}; for (void* p : tk) if (p) (void)hipFree(p); }
-  if (b->tk.h_link_dead) (void)hipHostFree(b->tk.h_link_dead);
-  if (b->tk.h_stage) (void)hipHostFree(b->tk.h_stage);
-  for (hipEvent_t e : b->tk.stage_ev) if (e) (void)hipEventDestroy(e);
-  host_stream_free(b);
-  if (b->r48.d_in16) (void)hipFree(b->r48.d_in16);
-  if (b->r48.d_out24) (void)hipFree(b->r48.d_out24);
-  rb_release(b);
-  silent_release(b);
   if (b->own_d_out) { b->wave.d_out = b->own_d_out; b->own_d_out = nullptr; }
   if (b->io_mapped) { b->wave.d_out = b->dev_d_out; b->phone.d_in = b->pitch.d_in = b->d_in; b->io_mapped = false; }  // (the modules free what they allocated)
   if (b->module_owned[0]) {  // hand the modules their own arrays back so that destroy() frees what it allocated
@@ -940,20 +892,7 @@ void BeatriceBatch_Destroy(BeatriceBatch* b) {
     for (int blk = 0; blk < B_NBLOCKS; ++blk) { swap_out(b->wave.d_perm[blk]); swap_out(b->wave.d_tile_slot[blk]); }
   }
   b->phone.destroy(); b->pitch.destroy(); b->wave.destroy();
-  void* dev[] = {b->d_in, b->d_cb_raw, b->d_cbT, b->d_cnorm, b->d_add_raw, b->d_frm_raw, b->d_kv_raw,
-                 b->d_w48, b->d_coef_down, b->d_coef_up, b->d_io48, b->d_hop_next, b->d_hop_wave};
-  if (b->h_io48) (void)hipHostFree(b->h_io48);
-  for (void* p : dev) if (p) (void)hipFree(p);
-  b->settings.release();
-  if (b->settings.d) (void)hipFree(b->settings.d);
-  if (b->h_in) (void)hipHostFree(b->h_in);
-  if (b->h_out) (void)hipHostFree(b->h_out);
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  for (auto& per_stage : b->ev_done) for (hipEvent_t e : per_stage) if (e) (void)hipEventDestroy(e);
-  for (hipStream_t st : b->stage_stream_own) if (st) (void)hipStreamDestroy(st);
-  if (b->owns_stream && b->stream) (void)hipStreamDestroy(b->stream);
-  delete b;
+  delete b;   // (everything the batch owns is freed here: synchronised, and with its device still current)
 }
 
 int BeatriceBatch_IsHealthy(const BeatriceBatch* b) { return b && b->ok ? 1 : 0; }
@@ -1318,9 +1257,8 @@ int BeatriceBatch_SetStream(BeatriceBatch* b, void* hip_stream) {
   BATCH_OPEN(b);
   (void)sync_all(b);
   drop_graph(b);
-  if (b->owns_stream) (void)hipStreamDestroy(b->stream);
+  b->stream_own.reset();
   b->stream = static_cast<hipStream_t>(hip_stream);
-  b->owns_stream = false;
   return 0;
 }
 void* BeatriceBatch_GetStream(const BeatriceBatch* b) { return b ? b->stream : nullptr; }
@@ -1351,14 +1289,13 @@ int BeatriceBatch_TimeTickLaunch(BeatriceBatch* b, int ticks, float* us_per_laun
   // ONE pair of events around `ticks` back-to-back launches (an event pair per launch adds two commands between
   // consecutive launches and reads ~5 us long against rocprofv3's kernel durations); the figure includes the boundary
   // between two ticks, which belongs to the launch's cost
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool ok = hip_ok(hipEventCreate(&ev[0]), "tick ev") && hip_ok(hipEventCreate(&ev[1]), "tick ev");
+  Event ev[2];
+  bool ok = ev[0].create("tick ev", true) && ev[1].create("tick ev", true);
   ok = ok && hip_ok(hipEventRecord(ev[0], b->stream), "tick ev0");
   for (int i = 0; i < ticks && ok; ++i) ok = tick_run(b, true);
   ok = ok && hip_ok(hipEventRecord(ev[1], b->stream), "tick ev1") && hip_ok(hipStreamSynchronize(b->stream), "tick time sync");
   float ms = 0;
   ok = ok && hip_ok(hipEventElapsedTime(&ms, ev[0], ev[1]), "tick elapsed");
-  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   if (!ok) return -2;
   *us_per_launch = (float)(1000.0 * ms / ticks);
   if (flops) *flops = b->tk.table_flops;
@@ -1386,7 +1323,7 @@ int BeatriceBatch_EnablePipelining(BeatriceBatch* b, int enable) {
   drop_graph(b);  // stages are captured on the streams they will run on
   set_plan(b, enable == 1 ? 2 : enable);  // 1 = the default depth
   for (int s = 1; s < b->n_stages && b->pipelined; ++s)  // every stream takes a hardware queue: only those in use exist
-    if (!b->stage_stream_own[s] && !make_stage_stream(&b->stage_stream_own[s], s)) return -2;
+    if (!b->stage_stream_own[s] && !make_stage_stream(b->stage_stream_own[s], s)) return -2;
   return 0;
 }
 void* BeatriceBatch_GetWaveStream(const BeatriceBatch* b) { return b ? wave_stream(b) : nullptr; }
@@ -1400,7 +1337,7 @@ int BeatriceBatch_Prepare(BeatriceBatch* b) {
   else for (int s = 0; s < b->n_stages && ok; ++s) ok = run_stage(b, s, -1);
   return ok ? 0 : -2;
 }
-float* BeatriceBatch_DeviceInput(BeatriceBatch* b) { return b && b->ok ? b->d_in : nullptr; }
+float* BeatriceBatch_DeviceInput(BeatriceBatch* b) { return b && b->ok ? b->d_in.get() : nullptr; }
 float* BeatriceBatch_DeviceOutput(BeatriceBatch* b) {
   const DeviceScope dev_(b ? b->device : -1);
   return b && b->ok && set_io_mapped(b, false) ? b->wave.d_out : nullptr;

@@ -44,24 +44,6 @@ static bool host_stream_wait(BeatriceBatch* b, const BeatriceBatch::HostStream::
     if (h.tick_of_ev[t % n] == t) return hip_ok(hipEventSynchronize(h.ev_tick[t % n]), "hs tick done");
   return false;
 }
-}  // extern "C"
-namespace {
-void host_stream_free(BeatriceBatch* b) {
-  BeatriceBatch::HostStream& h = b->hs;
-  for (hipEvent_t e : h.ev_in) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h.ev_out) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h.ev_tick) if (e) (void)hipEventDestroy(e);
-  h.ev_in.clear(); h.ev_out.clear(); h.ev_tick.clear();
-  if (h.s_in) (void)hipStreamDestroy(h.s_in);
-  if (h.s_out) (void)hipStreamDestroy(h.s_out);
-  if (h.d_in) (void)hipFree(h.d_in);
-  if (h.d_out) (void)hipFree(h.d_out);
-  if (h.h_in) (void)hipHostFree(h.h_in);
-  if (h.h_out) (void)hipHostFree(h.h_out);
-  h = BeatriceBatch::HostStream{};
-}
-}  // namespace
-extern "C" {
 int BeatriceBatch_EnableHostStreaming(BeatriceBatch* b, int enable) {
   BATCH_OPEN(b);
   if (enable) BATCH_GATE(b, Entry::EnableHostStreaming_1);
@@ -73,29 +55,23 @@ int BeatriceBatch_EnableHostStreaming(BeatriceBatch* b, int enable) {
     const int rc = tick_enable(b, false);
     if (rc) return rc;
     const int rb = bind_io(b, nullptr, nullptr, 0);
-    host_stream_free(b);
+    h = {};
     return rb;
   }
-  h.n_slots = b->tk.plan.count() + 8;
+  BeatriceBatch::HostStream nh;   // (moved into place once everything is there)
+  nh.n_slots = b->tk.plan.count() + 8;
   const size_t n_in = (size_t)b->B * b->H * B_IN_HOP, n_out = (size_t)b->B * b->H * B_OUT_HOP;
-  bool ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&h.d_in), sizeof(float) * n_in * h.n_slots), "hs d_in") &&
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&h.d_out), sizeof(float) * n_out * h.n_slots), "hs d_out") &&
-            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h.h_in), sizeof(float) * n_in * h.n_slots, hipHostMallocDefault), "hs h_in") &&
-            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h.h_out), sizeof(float) * n_out * h.n_slots, hipHostMallocDefault), "hs h_out") &&
-            hip_ok(hipMemset(h.d_in, 0, sizeof(float) * n_in * h.n_slots), "hs zero") &&
-            hip_ok(hipStreamCreateWithFlags(&h.s_in, hipStreamNonBlocking), "hs s_in") &&
-            hip_ok(hipStreamCreateWithFlags(&h.s_out, hipStreamNonBlocking), "hs s_out");
-  h.ev_in.assign(h.n_slots, nullptr); h.ev_out.assign(h.n_slots, nullptr); h.ev_tick.assign(tick::kRing, nullptr);
-  for (auto* v : {&h.ev_in, &h.ev_out, &h.ev_tick})
-    for (hipEvent_t& e : *v) ok = ok && hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hs event");
-  h.tick_of_ev.assign(tick::kRing, -1);
-  h.mapped = bhip::meas_env("BEATRICE_HIP_HS_COPIES") == nullptr;   // A/B switch: copies on two more streams instead
-  if (ok && h.mapped) std::memset(h.h_in, 0, sizeof(float) * n_in * h.n_slots);
-  ok = ok && bind_io(b, h.mapped ? h.h_in : h.d_in, h.mapped ? h.h_out : h.d_out, h.n_slots) == 0 && tick_enable(b, true) == 0;
-  if (!ok) { (void)tick_enable(b, false); (void)bind_io(b, nullptr, nullptr, 0); host_stream_free(b); return -2; }
-  h.pending.clear();
-  h.fed = 0;
-  h.rec[0] = h.rec[1] = -1;
+  bool ok = nh.d_in.alloc(n_in * nh.n_slots, "hs d_in") && nh.d_out.alloc(n_out * nh.n_slots, "hs d_out", false) &&
+            nh.h_in.alloc(n_in * nh.n_slots, "hs h_in") && nh.h_out.alloc(n_out * nh.n_slots, "hs h_out") &&
+            nh.s_in.create("hs s_in") && nh.s_out.create("hs s_out");
+  nh.ev_in.resize(nh.n_slots); nh.ev_out.resize(nh.n_slots); nh.ev_tick.resize(tick::kRing);
+  for (auto* v : {&nh.ev_in, &nh.ev_out, &nh.ev_tick})
+    for (Event& e : *v) ok = ok && e.create("hs event");
+  nh.tick_of_ev.assign(tick::kRing, -1);
+  nh.mapped = bhip::meas_env("BEATRICE_HIP_HS_COPIES") == nullptr;   // A/B switch: copies on two more streams instead
+  ok = ok && bind_io(b, nh.mapped ? nh.h_in.get() : nh.d_in.get(), nh.mapped ? nh.h_out.get() : nh.d_out.get(), nh.n_slots) == 0 && tick_enable(b, true) == 0;
+  if (!ok) { (void)tick_enable(b, false); (void)bind_io(b, nullptr, nullptr, 0); return -2; }
+  h = std::move(nh);
   h.on = true;
   return 0;
 }

@@ -206,20 +206,14 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
     } else {
       desc = tb->in_span_order();
     }
-    auto upload = [&](const std::vector<fuse::WgDesc>& v, fuse::WgDesc*& d_desc, size_t& cap) {
-      if (v.size() > cap) {
-        if (d_desc) (void)hipFree(d_desc);
-        d_desc = nullptr;
-        cap = 0;
-        BHIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_desc), sizeof(fuse::WgDesc) * v.size()));
-        cap = v.size();
-      }
+    auto upload = [&](const std::vector<fuse::WgDesc>& v, DevBuf<fuse::WgDesc>& d_desc) {
+      if (v.size() > d_desc.size() && !d_desc.alloc(v.size(), "tick dispatch order", false)) return false;
       if (!v.empty()) BHIP_TRY(hipMemcpy(d_desc, v.data(), sizeof(fuse::WgDesc) * v.size(), hipMemcpyHostToDevice));
       return true;
     };
     if (!sparse) {   // (the order of partly filled ticks: tick_launch)
       const std::vector<fuse::WgDesc> plain = tb->in_span_order();
-      if (!upload(plain, k.d_desc_plain, k.desc_plain_cap)) return false;
+      if (!upload(plain, k.d_desc_plain)) return false;
       k.table_total_plain = (int)plain.size();
       // the fill / drain shapes without the empty stages' workgroups (tick::State::d_desc_ranges)
       for (auto& row : k.range_n) for (int& n : row) n = 0;
@@ -244,15 +238,14 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
             }
             k.range_n[shape][s0] = (int)(all.size() - k.range_off[shape][s0]);
           }
-        if (!upload(all, k.d_desc_ranges, k.desc_ranges_cap)) return false;
+        if (!upload(all, k.d_desc_ranges)) return false;
       }
     }
     tb->t.total = (int)desc.size();   // (two_halves may add filler indices)
-    if (!upload(desc, sparse ? k.d_desc_sparse : k.d_desc, sparse ? k.desc_sparse_cap : k.desc_cap)) return false;
+    if (!upload(desc, sparse ? k.d_desc_sparse : k.d_desc)) return false;
   }
   if (bhip::meas_env("BEATRICE_HIP_TICK_TRACE")) {
-    if (k.d_trace) (void)hipFree(k.d_trace);
-    BHIP_TRY(hipMalloc(reinterpret_cast<void**>(&k.d_trace), sizeof(unsigned long long) * 3 * tb->t.total));
+    if (!k.d_trace.alloc((size_t)3 * tb->t.total, "tick trace", false)) return false;
     tb->t.trace = k.d_trace;
   }
   if (sparse) {
@@ -289,14 +282,14 @@ bool tick_build_table(BeatriceBatch* b, const bool sparse = false) {
 // the launch of one tick: the table kernel of the batch's hops per step
 static void tick_launch(BeatriceBatch* b, const bool sparse, const bool full, hipStream_t st, const fuse::StepPairs& pairs) {
   tick::State& k = b->tk;
-  const void* t = sparse ? k.d_table_sparse : k.d_table;
+  const void* t = sparse ? k.d_table_sparse.get() : k.d_table.get();
   // full = every stage has a step: the order that confines the bodies with the weights to halves of the chip; a partly filled tick
   // (fill, drain) runs the same table in plain span order -- without the workgroups of its empty stages where the occupied stages
   // are 0 .. k or k .. last (tick::State::d_desc_ranges)
-  const fuse::WgDesc* desc = sparse ? k.d_desc_sparse : (full ? k.d_desc : k.d_desc_plain);
+  const fuse::WgDesc* desc = sparse ? k.d_desc_sparse.get() : (full ? k.d_desc.get() : k.d_desc_plain.get());
   int total = sparse ? k.table_sparse_total : (full ? k.table_total : k.table_total_plain);
   static const bool no_ranges = bhip::meas_env("BEATRICE_HIP_TICK_NO_RANGES") != nullptr;   // A/B switch for measurements
-  if (!sparse && !full && !no_ranges && k.d_desc_ranges != nullptr) {
+  if (!sparse && !full && !no_ranges && k.d_desc_ranges.get() != nullptr) {
     const int n_stages = k.plan.count();
     int lo = n_stages, hi = -1, occupied = 0;
     for (int s = 0; s < n_stages; ++s) if (pairs.hop[s] >= 0) { lo = s < lo ? s : lo; hi = s; ++occupied; }
@@ -355,8 +348,8 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
       // (the batch's two-deep mirror would make every second change wait for the copy of the change before it); the
       // tick's prologue kernel reads the staging copy straight from host memory (tick.hip.h)
       const int si = serial % State::kStaging;
-      if (k.stage_pending[si]) { if (!hip_ok(hipEventSynchronize(k.stage_ev[si]), "tick settings staging")) return false; }
-      unsigned char* src = k.h_stage + (size_t)si * k.snap_bytes;
+      unsigned char* src = k.stage.claim(si);
+      if (!src) return false;
       std::memcpy(src, b->settings.h + off, len);
       upload = Copy{dst, src, (int)len};
       upload_stage = si;
@@ -379,11 +372,11 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
     BeatriceBatch::SilentRule& sr = b->silent;
     if (!k.ragged && sr.on && sr.any_next) {   // the first stream to stand still: from here on every stream has its own counter
       if (!k.d_hopv) {
-        k.row = (b->B + 3) & ~3;
-        if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&k.d_hopv), sizeof(int) * kRing * k.row), "tick hopv") ||
-            !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&k.h_hopv), sizeof(int) * State::kStaging * k.row, hipHostMallocDefault), "tick hopv staging"))
-          return false;
-        for (hipEvent_t& e : k.hv_ev) if (!hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "tick hopv event")) return false;
+        const int row = (b->B + 3) & ~3;
+        DevBuf<int> d_hopv;
+        StagedRing<int> hopv;
+        if (!d_hopv.alloc((size_t)kRing * row, "tick hopv", false) || !hopv.alloc(State::kStaging, row, "tick hopv staging")) return false;
+        k.row = row; k.d_hopv = std::move(d_hopv); k.hopv = std::move(hopv);
       }
       k.hop_s.assign(b->B, b->hop_host);
       k.ragged = true;
@@ -392,8 +385,8 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
     k.step_ragged[u % kRing] = k.ragged;
     if (k.ragged) {
       const int si = (int)(u % State::kStaging);
-      if (k.hv_pending[si]) { if (!hip_ok(hipEventSynchronize(k.hv_ev[si]), "tick hopv staging")) return false; k.hv_pending[si] = false; }
-      int* h = k.h_hopv + (size_t)si * k.row;
+      int* h = k.hopv.claim(si);
+      if (!h) return false;
       for (int s = 0; s < b->B; ++s) {
         const bool out = sr.any_next && sr.next[s];
         h[s] = out ? -1 : k.hop_s[s];
@@ -436,14 +429,8 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
     for (int i = 0; i < p.n_copies; ++i) { p.first_chunk[i] = chunks; chunks += (p.copy[i].bytes + kCopyChunk - 1) / kCopyChunk; }
     p.first_chunk[p.n_copies] = chunks;
     hipLaunchKernelGGL(prologue_kernel, dim3(chunks), dim3(256), 0, st, p);
-    if (upload_stage >= 0) {
-      if (!hip_ok(hipEventRecord(k.stage_ev[upload_stage], st), "tick settings event")) return false;
-      k.stage_pending[upload_stage] = true;
-    }
-    if (hv_stage >= 0) {
-      if (!hip_ok(hipEventRecord(k.hv_ev[hv_stage], st), "tick hopv event")) return false;
-      k.hv_pending[hv_stage] = true;
-    }
+    if (upload_stage >= 0 && !k.stage.mark(upload_stage, st)) return false;
+    if (hv_stage >= 0 && !k.hopv.mark(hv_stage, st)) return false;
   }
   if (b->r48.on && (feeding || b->r48.deferred_slot >= 0)) {
     // one launch for both ends of the 48 kHz wrapper: the block entering the pipeline -> its 16 kHz hop, straight into the
@@ -471,7 +458,7 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
   }
   prof.lap(3);
   fuse::StepPairs pairs;
-  pairs.hopv = k.ragged ? k.d_hopv : nullptr;
+  pairs.hopv = k.ragged ? k.d_hopv.get() : nullptr;
   pairs.n_streams = k.row;
   for (int s = 0; s < fuse::kMaxStepPairs; ++s) {
     pairs.hop[s] = s < p.n_stages ? p.hop[s] : -1; pairs.io[s] = s < p.n_stages ? p.io[s] : 0;
@@ -532,14 +519,16 @@ static bool tick_relevel(BeatriceBatch* b) {
           if (r->m > kMaxRotateSlots) return false;
           rings.push_back(FreezeRing{r->base, r->n * r->C, r->m, 0});
         }
-      k.n_ring_table = (int)rings.size();
-      if (!hip_ok(hipMalloc(&k.d_ring_table, sizeof(FreezeRing) * rings.size()), "ring table") ||
-          !hip_ok(hipMemcpy(k.d_ring_table, rings.data(), sizeof(FreezeRing) * rings.size(), hipMemcpyHostToDevice), "ring table up") ||
-          !hip_ok(hipMalloc(reinterpret_cast<void**>(&k.d_shift), sizeof(int) * b->B), "ring shifts"))
+      DevBuf<FreezeRing> d_rings;
+      DevBuf<int> d_shift;
+      if (!d_rings.alloc(rings.size(), "ring table", false) ||
+          !hip_ok(hipMemcpy(d_rings, rings.data(), sizeof(FreezeRing) * rings.size(), hipMemcpyHostToDevice), "ring table up") ||
+          !d_shift.alloc(b->B, "ring shifts", false))
         return false;
+      k.n_ring_table = (int)rings.size(); k.d_ring_table = std::move(d_rings); k.d_shift = std::move(d_shift);
     }
     if (!hip_ok(hipMemcpyAsync(k.d_shift, shift.data(), sizeof(int) * b->B, hipMemcpyHostToDevice, b->stream), "ring shifts up")) return false;   // (pageable source: staged before the call returns)
-    hipLaunchKernelGGL(ring_rotate_kernel, dim3(k.n_ring_table, b->B), dim3(256), 0, b->stream, static_cast<const FreezeRing*>(k.d_ring_table), k.d_shift);
+    hipLaunchKernelGGL(ring_rotate_kernel, dim3(k.n_ring_table, b->B), dim3(256), 0, b->stream, k.d_ring_table.get(), k.d_shift.get());
     if (!hip_ok(hipGetLastError(), "ring rotate")) return false;
   }
   k.hop_s.assign(b->B, b->hop_host);
@@ -556,15 +545,14 @@ bool rb_post(BeatriceBatch* b, const BeatriceBatch::ResidentBlocks::Job& j) {
   const int slot = (int)(j.call % r.n_slots), ge = (int)(j.call % r.ring);
   if (r.ragged)   // clocks per stream: the call's records name every stream's directions, sample count and block
     hipLaunchKernelGGL(wrapn::wrapr_post_kernel, dim3(b->B), dim3(256), 0, b->stream, r.d_out24, b->B, r.d_map, r.map_ring, b->d_wrap,
-                       r.h_gains + (size_t)ge * 2 * b->B + b->B, b->rw.d_taps, r.h_rs + (size_t)ge * b->B,
+                       r.gains.host(ge) + b->B, b->rw.d_taps.get(), r.h_rs + (size_t)ge * b->B,
                        r.d_out + (size_t)slot * b->B * r.cell, r.channels);
   else   // (the gain segments where the host wrote them: pinned memory)
     hipLaunchKernelGGL(wrapn::wrap_post_kernel, dim3(b->B), dim3(256), 0, b->stream, r.d_out24, r.io_slots, b->B, b->H, j.t0, b->d_wrap,
-                       r.h_gains + (size_t)ge * 2 * b->B + b->B, b->d_wrap_taps + (j.dout.decimate ? 0 : nt), j.dout,
+                       r.gains.host(ge) + b->B, b->d_wrap_taps + (j.dout.decimate ? 0 : nt), j.dout,
                        r.d_out + (size_t)slot * b->B * r.channels * r.n, r.channels);
   // (the event frees the ring entry for the host)
-  if (!hip_ok(hipEventRecord(r.gain_ev[ge], b->stream), "wrapper gain event")) return false;
-  r.ev_recorded[ge] = 1;
+  if (!r.gains.mark(ge, b->stream)) return false;
   return hip_ok(hipGetLastError(), "wrapper output half");
 }
 bool tick_drain(BeatriceBatch* b) {
@@ -614,23 +602,22 @@ int tick_enable(BeatriceBatch* b, bool on) {
     if (!sync_all(b)) return -2;
     if (b->pipelined) { drop_graph(b); set_plan(b, 1); }
     k.snap_bytes = b->off.front_bytes + b->off.wave_bytes;
-    if (!k.d_table) {
+    if (!k.d_table) {   // (each group into locals first: a failure half-way leaves the batch as it was)
       const size_t tab_bytes = std::max(std::max(sizeof(Ops<1>::Tab), sizeof(Ops<2>::Tab)), sizeof(Ops<4>::Tab));
-      if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&k.d_table), tab_bytes), "tick table") ||
-          !hip_ok(hipMalloc(reinterpret_cast<void**>(&k.d_table_sparse), tab_bytes), "tick sparse table") ||
-          !hip_ok(hipMalloc(reinterpret_cast<void**>(&k.d_snap), k.snap_bytes * kRing), "tick snapshots") ||
-          !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&k.h_stage), k.snap_bytes * State::kStaging, hipHostMallocDefault), "tick staging"))
+      DevBuf<unsigned char> table, table_sparse, snap;
+      StagedRing<unsigned char> stage;
+      if (!table.alloc(tab_bytes, "tick table", false) || !table_sparse.alloc(tab_bytes, "tick sparse table", false) ||
+          !snap.alloc(k.snap_bytes * kRing, "tick snapshots", false) || !stage.alloc(State::kStaging, k.snap_bytes, "tick staging"))
         return -2;
-      for (hipEvent_t& e : k.stage_ev) if (!hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "tick staging event")) return -2;
+      k.d_table = std::move(table); k.d_table_sparse = std::move(table_sparse); k.d_snap = std::move(snap); k.stage = std::move(stage);
     }
     if (b->H > 1 && !k.d_link_p) {   // the granules between the GRU cells of a step's hops (tick.hip.h); tag 0 = never written
-      const size_t nq = (size_t)(b->H - 1) * b->B * 128, np = (size_t)(b->H - 1) * b->B * 256;
-      if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&k.d_link_q), sizeof(unsigned long long) * nq), "tick gru link") ||
-          !hip_ok(hipMalloc(reinterpret_cast<void**>(&k.d_link_p), sizeof(unsigned long long) * np), "tick gru link") ||
-          !hip_ok(hipMemset(k.d_link_q, 0, sizeof(unsigned long long) * nq), "tick gru link") || !hip_ok(hipMemset(k.d_link_p, 0, sizeof(unsigned long long) * np), "tick gru link") ||
-          !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&k.h_link_dead), sizeof(int), hipHostMallocDefault), "tick gru link flag"))
+      DevBuf<unsigned long long> link_q, link_p;
+      PinnedBuf<int> dead;
+      if (!link_q.alloc((size_t)(b->H - 1) * b->B * 128, "tick gru link") || !link_p.alloc((size_t)(b->H - 1) * b->B * 256, "tick gru link") ||
+          !dead.alloc(1, "tick gru link flag"))
         return -2;
-      *k.h_link_dead = 0;
+      k.d_link_q = std::move(link_q); k.d_link_p = std::move(link_p); k.h_link_dead = std::move(dead);
     }
     // the plain-order K / V copies the quad bodies read (rowchain.hip.h block_bq_body) exist in tick mode only: ~3 MB per
     // speaker that the in-order, stage-pipelined and large-batch modes never read

@@ -9,10 +9,10 @@ static bool step_48k(BeatriceBatch* b, const float* d_in48, float* d_out48, int 
   int flag_slot = -1;
   if (sr.on && sr.any_next) {   // this step's flags travel to the device through a ring of staging copies; a slot is reused only
     const int e = (int)(sr.steps % BeatriceBatch::SilentRule::kDepth);   // after the step that read it has finished (its event)
-    if (sr.flag_pending[e]) { BHIP_TRY(hipEventSynchronize(sr.flag_ev[e])); sr.flag_pending[e] = false; }
-    unsigned char* h = sr.h_flags + (size_t)e * b->B;
+    unsigned char* h = sr.flags.claim(e);
+    if (!h) return false;
     std::memcpy(h, sr.next.data(), b->B);
-    unsigned char* d = sr.d_flags + (size_t)e * b->B;
+    unsigned char* d = sr.flags.dev(e);
     BHIP_TRY(hipMemcpyAsync(d, h, b->B, hipMemcpyHostToDevice, b->stream));
     frozen = d;
     flag_slot = e;
@@ -35,20 +35,10 @@ static bool step_48k(BeatriceBatch* b, const float* d_in48, float* d_out48, int 
     hipLaunchKernelGGL(freeze_fix_kernel, dim3(sr.n_rings, b->B), dim3(256), 0, b->stream, sr.d_rings, sr.d_keep, b->B, frozen, b->last_hop,
                        b->pitch.d_prev_q, sr.d_keep_prev_q);
   hipLaunchKernelGGL(wrap48_latch_kernel, dim3((b->B * 240 + 255) / 256), dim3(256), 0, b->stream, b->d_w48, b->wave.d_out, b->B, frozen);
-  if (flag_slot >= 0) { BHIP_TRY(hipEventRecord(sr.flag_ev[flag_slot], b->stream)); sr.flag_pending[flag_slot] = true; }
+  if (flag_slot >= 0 && !sr.flags.mark(flag_slot, b->stream)) return false;
   return hip_ok(hipGetLastError(), "wrap48");
 }
 static bool freeze_prepare(BeatriceBatch* b);
-static void silent_release(BeatriceBatch* b) {
-  BeatriceBatch::SilentRule& sr = b->silent;
-  for (hipEvent_t& e : sr.flag_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  if (sr.d_flags) (void)hipFree(sr.d_flags);
-  if (sr.h_flags) (void)hipHostFree(sr.h_flags);
-  if (sr.d_rings) (void)hipFree(sr.d_rings);
-  if (sr.d_keep) (void)hipFree(sr.d_keep);
-  if (sr.d_keep_prev_q) (void)hipFree(sr.d_keep_prev_q);
-  sr = BeatriceBatch::SilentRule{};
-}
 // The shell's rule "a block whose down-mix is all zeros is not converted" (reference src/vst/processor.cc:204-214), per stream,
 // for the in-order 48 kHz blocks: BeatriceBatch_ConvertBlocks48k (host buffers) finds the silent streams itself, exactly as the
 // shell does (every sample of (L + R) * 0.5, or of L, equal to 0.0f); with device buffers the caller names them for the next
@@ -63,7 +53,7 @@ int BeatriceBatch_EnableSilentBlockRule(BeatriceBatch* b, int enable) {
   BATCH_GATE(b, enable ? Entry::EnableSilentBlockRule_1 : Entry::EnableSilentBlockRule_0);
   BeatriceBatch::SilentRule& sr = b->silent;
   if (!enable) {
-    if (sr.on) { (void)sync_all(b); if (b->rw.ready) sr.on = false; else silent_release(b); }   // (the per-stream wrapper keeps the freeze machinery)
+    if (sr.on) { (void)sync_all(b); if (b->rw.ready) sr.on = false; else sr = {}; }   // (the per-stream wrapper keeps the freeze machinery)
     return 0;
   }
   if (sr.on) return 0;
@@ -76,7 +66,7 @@ int BeatriceBatch_EnableSilentBlockRule(BeatriceBatch* b, int enable) {
     return 0;
   }
   if (!sync_all(b)) return -2;   // the in-order chain, one block per step
-  if (!freeze_prepare(b)) { silent_release(b); return -2; }
+  if (!freeze_prepare(b)) return -2;
   sr.on = true;
   drop_graph(b);
   return 0;
@@ -94,15 +84,17 @@ static bool freeze_prepare(BeatriceBatch* b) {
       if (r->m == 1) { f.keep_off = keep; keep += (size_t)b->B * f.slot_floats; }
       rings.push_back(f);
     }
+  DevBuf<FreezeRing> d_rings;
+  DevBuf<float> d_keep;
+  DevBuf<int> d_keep_prev_q;
+  StagedRing<unsigned char> flags;
+  if (!d_rings.alloc(rings.size(), "silent rings", false) ||
+      !hip_ok(hipMemcpy(d_rings, rings.data(), sizeof(FreezeRing) * rings.size(), hipMemcpyHostToDevice), "silent rings up") ||
+      !d_keep.alloc(std::max<size_t>(keep, 1), "silent keep", false) || !d_keep_prev_q.alloc(b->B, "silent prev_q", false) ||
+      !flags.alloc(BeatriceBatch::SilentRule::kDepth, b->B, "silent flags", true))
+    return false;
   sr.n_rings = (int)rings.size();
-  bool ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&sr.d_rings), sizeof(FreezeRing) * rings.size()), "silent rings") &&
-            hip_ok(hipMemcpy(sr.d_rings, rings.data(), sizeof(FreezeRing) * rings.size(), hipMemcpyHostToDevice), "silent rings up") &&
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&sr.d_keep), sizeof(float) * std::max<size_t>(keep, 1)), "silent keep") &&
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&sr.d_keep_prev_q), sizeof(int) * b->B), "silent prev_q") &&
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&sr.d_flags), BeatriceBatch::SilentRule::kDepth * (size_t)b->B), "silent flags") &&
-            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&sr.h_flags), BeatriceBatch::SilentRule::kDepth * (size_t)b->B, hipHostMallocDefault), "silent flags host");
-  for (hipEvent_t& e : sr.flag_ev) ok = ok && hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "silent flag event");
-  if (!ok) return false;
+  sr.d_rings = std::move(d_rings); sr.d_keep = std::move(d_keep); sr.d_keep_prev_q = std::move(d_keep_prev_q); sr.flags = std::move(flags);
   sr.next.assign(b->B, 0);
   sr.any_next = false;
   return true;
@@ -130,26 +122,21 @@ int BeatriceBatch_BindResidentIO48k(BeatriceBatch* b, const float* d_in48, float
     const int rc = tick_enable(b, false);
     if (rc) return rc;
     (void)bind_io(b, nullptr, nullptr, 0);
-    if (r.d_in16) (void)hipFree(r.d_in16);
-    if (r.d_out24) (void)hipFree(r.d_out24);
-    r = BeatriceBatch::Resident48{};
+    r = {};
   }
   if (!bind) return 0;
   BATCH_GATE(b, Entry::BindResidentIO48k_bind);   // (again: the mode the batch is in now that it has left F)
   if (!d_in48 || !d_out48 || channels < 1 || channels > 2 || n_slots < b->tk.plan.count() + 1) return -1;
   // (with H hops per step a slot holds H blocks per stream, [B][H][channels][480], and a call converts them all)
-  bool ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_in16), sizeof(float) * n_slots * b->B * b->H * B_IN_HOP), "r48 in16") &&
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_out24), sizeof(float) * n_slots * b->B * b->H * B_OUT_HOP), "r48 out24") &&
-            hip_ok(hipMemset(r.d_in16, 0, sizeof(float) * n_slots * b->B * b->H * B_IN_HOP), "r48 zero");
-  ok = ok && bind_io(b, r.d_in16, r.d_out24, n_slots) == 0 && tick_enable(b, true) == 0;
+  DevBuf<float> d_in16, d_out24;
+  const bool ok = d_in16.alloc((size_t)n_slots * b->B * b->H * B_IN_HOP, "r48 in16") && d_out24.alloc((size_t)n_slots * b->B * b->H * B_OUT_HOP, "r48 out24", false) &&
+                  bind_io(b, d_in16, d_out24, n_slots) == 0 && tick_enable(b, true) == 0;
   if (!ok) {
     (void)tick_enable(b, false);
     (void)bind_io(b, nullptr, nullptr, 0);
-    if (r.d_in16) (void)hipFree(r.d_in16);
-    if (r.d_out24) (void)hipFree(r.d_out24);
-    r = BeatriceBatch::Resident48{};
     return -2;
   }
+  r.d_in16 = std::move(d_in16); r.d_out24 = std::move(d_out24);
   r.d_in48 = d_in48; r.d_out48 = d_out48; r.channels = channels; r.n_slots = n_slots; r.on = true;
   return 0;
 }
@@ -203,17 +190,21 @@ int BeatriceBatch_ConfigureWrapper(BeatriceBatch* b, double sample_rate) {
   const size_t nt = b->wrap.taps_down.size();
   bool ok = true;
   if (!b->d_wrap) {
-    ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_wrap), sizeof(wrapn::StreamState) * B), "wrap state") &&
-         hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_wrap_inner), sizeof(float) * B * kInnerStride), "wrap inner") &&
-         hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_wrap_io), sizeof(float) * B * 4 * wrapn::kMaxSamples), "wrap io") &&
-         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_wrap_io), sizeof(float) * B * 4 * wrapn::kMaxSamples, hipHostMallocDefault), "wrap io host") &&
-         b->wrap_gains.alloc_host(2 * (size_t)B) &&
-         hip_ok(hipMalloc(reinterpret_cast<void**>(&b->wrap_gains.d), sizeof(wrapn::GainSeg) * 2 * B), "wrap gains");
-    b->gain_in.assign(B, wrapn::GainClock());
-    b->gain_out.assign(B, wrapn::GainClock());
+    DevBuf<wrapn::StreamState> state;
+    DevBuf<float> inner, io;
+    PinnedBuf<float> h_io;
+    Mirror<wrapn::GainSeg> gains;
+    ok = state.alloc(B, "wrap state", false) && inner.alloc((size_t)B * kInnerStride, "wrap inner", false) &&
+         io.alloc((size_t)B * 4 * wrapn::kMaxSamples, "wrap io", false) && h_io.alloc((size_t)B * 4 * wrapn::kMaxSamples, "wrap io host") &&
+         gains.alloc(2 * (size_t)B, 2 * (size_t)B, "wrap gains", false);
+    if (ok) {
+      b->d_wrap = std::move(state); b->d_wrap_inner = std::move(inner); b->d_wrap_io = std::move(io); b->h_wrap_io = std::move(h_io);
+      b->wrap_gains = std::move(gains);
+      b->gain_in.assign(B, wrapn::GainClock());
+      b->gain_out.assign(B, wrapn::GainClock());
+    }
   }
-  if (b->d_wrap_taps) { (void)hipFree(b->d_wrap_taps); b->d_wrap_taps = nullptr; }
-  ok = ok && hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_wrap_taps), sizeof(float) * 2 * nt), "wrap taps") &&
+  ok = ok && b->d_wrap_taps.alloc(2 * nt, "wrap taps", false) &&
        hip_ok(hipMemcpy(b->d_wrap_taps, b->wrap.taps_down.data(), sizeof(float) * nt, hipMemcpyHostToDevice), "taps down") &&
        hip_ok(hipMemcpy(b->d_wrap_taps + nt, b->wrap.taps_up.data(), sizeof(float) * nt, hipMemcpyHostToDevice), "taps up") &&
        hip_ok(hipMemset(b->d_wrap, 0, sizeof(wrapn::StreamState) * B), "wrap state0") && hip_ok(hipDeviceSynchronize(), "wrap sync");
@@ -327,22 +318,22 @@ int BeatriceBatch_ConfigureWrapperRates(BeatriceBatch* b, const double* rates) {
   if (!b->d_wrap) { const int rc = BeatriceBatch_ConfigureWrapper(b, rates[0]); if (rc) return rc; }
   if (!freeze_prepare(b)) return -2;
   std::vector<float> taps;
-  r.taps_down_off.clear(); r.taps_up_off.clear();
+  std::vector<int> taps_down_off, taps_up_off;
   for (const wrapn::WrapPlan& p : classes) {
-    r.taps_down_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_down.begin(), p.taps_down.end());
-    r.taps_up_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_up.begin(), p.taps_up.end());
+    taps_down_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_down.begin(), p.taps_down.end());
+    taps_up_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_up.begin(), p.taps_up.end());
   }
-  if (r.d_taps) { (void)hipFree(r.d_taps); r.d_taps = nullptr; }
-  bool ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_taps), sizeof(float) * taps.size()), "ragged taps") &&
-            hip_ok(hipMemcpy(r.d_taps, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice), "ragged taps up");
-  if (ok && !r.d_rs) {
-    ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_rs), sizeof(wrapn::RagStream) * r.kStage * B), "ragged records") &&
-         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&r.h_rs), sizeof(wrapn::RagStream) * r.kStage * B, hipHostMallocDefault), "ragged records host") &&
-         hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_frozen), (size_t)wrapn::kMaxChunks * B), "ragged flags");
-    for (hipEvent_t& e : r.ev) ok = ok && hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "ragged event");
-  }
+  DevBuf<float> d_taps;
+  StagedRing<wrapn::RagStream> rs;
+  DevBuf<unsigned char> d_frozen;
+  bool ok = d_taps.alloc(taps.size(), "ragged taps", false) &&
+            hip_ok(hipMemcpy(d_taps, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice), "ragged taps up");
+  const bool first = r.rs.entries() == 0;   // (the staging of the records is built once; the taps with every call)
+  if (first) ok = ok && rs.alloc(r.kStage, B, "ragged records", true) && d_frozen.alloc((size_t)wrapn::kMaxChunks * B, "ragged flags", false);
   ok = ok && hip_ok(hipMemset(b->d_wrap, 0, sizeof(wrapn::StreamState) * B), "ragged state0") && hip_ok(hipDeviceSynchronize(), "ragged sync");
   if (!ok) return -2;
+  r.d_taps = std::move(d_taps); r.taps_down_off = taps_down_off; r.taps_up_off = taps_up_off;
+  if (first) { r.rs = std::move(rs); r.d_frozen = std::move(d_frozen); }
   r.classes = classes;
   r.cls = cls;
   r.clk.assign(B, BeatriceBatch::RaggedWrap::Clock{0, 0, 0});
@@ -405,8 +396,8 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
     total += (size_t)channels * n_samples[s];
   }
   const int e = (int)(r.calls % r.kStage);
-  if (r.pending[e]) { if (!hip_ok(hipEventSynchronize(r.ev[e]), "ragged staging")) return -2; r.pending[e] = false; }
-  RagStream* rs = r.h_rs + (size_t)e * B;
+  RagStream* rs = r.rs.claim(e);
+  if (!rs) return -2;
   GainSeg* seg = b->wrap_gains.h;
   int max_chunks = 0;
   size_t off = 0;
@@ -440,7 +431,7 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
     max_chunks = std::max(max_chunks, nc);
   }
   // uploads: the per-stream records of this call, the gain segments, the audio
-  RagStream* d_rs = r.d_rs + (size_t)e * B;
+  RagStream* d_rs = r.rs.dev(e);
   bool ok = hip_ok(hipMemcpyAsync(d_rs, rs, sizeof(RagStream) * B, hipMemcpyHostToDevice, st), "ragged records up");
   { const size_t o0 = 0, len = 2 * (size_t)B; GainSeg* dst = nullptr; ok = ok && b->wrap_gains.push_parts(st, 1, &o0, &len, &dst); }
   b->wrap_gains_constant = false;
@@ -480,8 +471,7 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
   }
   if (ok) {
     hipLaunchKernelGGL(wrapr_out_kernel, dim3(B), dim3(256), 0, st, b->d_wrap_inner, kInnerStride, b->d_wrap, b->wrap_gains.d + B, r.d_taps, d_rs, d_out, channels);
-    ok = hip_ok(hipGetLastError(), "ragged wrapper launch") && hip_ok(hipEventRecord(r.ev[e], st), "ragged event");
-    r.pending[e] = ok;
+    ok = hip_ok(hipGetLastError(), "ragged wrapper launch") && r.rs.mark(e, st);
   }
   r.calls += 1;
   ok = ok && hip_ok(hipMemcpyAsync(h_out, d_out, sizeof(float) * std::max<size_t>(total, 1), hipMemcpyDeviceToHost, st), "ragged out");
@@ -497,16 +487,20 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
 // 480-sample accumulation, a model hop into the tick pipeline every time it fills (one tick per hop, at least one tick per
 // call so that a hop is out of the pipeline TickStages() - 1 calls after it went in); then the output half of the call made
 // `delay` = TickStages() - 1 calls ago, into ITS slot of d_out.  Everything that is control is on the host, as in wrap_chunk.
-static void rb_release(BeatriceBatch* b) {
-  BeatriceBatch::ResidentBlocks& r = b->rb;
-  if (r.d_in16) (void)hipFree(r.d_in16);
-  if (r.d_out24) (void)hipFree(r.d_out24);
-  if (r.h_gains) (void)hipHostFree(r.h_gains);
-  if (r.gain_ev) { for (int i = 0; i < r.ring; ++i) if (r.gain_ev[i]) (void)hipEventDestroy(r.gain_ev[i]); delete[] r.gain_ev; }
-  if (r.h_rs) (void)hipHostFree(r.h_rs);
-  if (r.d_map) (void)hipFree(r.d_map);
-  if (r.d_zero) (void)hipFree(r.d_zero);
-  r = BeatriceBatch::ResidentBlocks{};
+// What both forms of the resident blocks bind, all or nothing: the ticks' resident 16 / 24 kHz slots and the gain ring of `nr` (the caller has set
+// its delay, ring, H and io_slots, and allocated what only its form has), resident I/O on those slots, tick mode.  `nr` then becomes the batch's.
+static bool rb_bind(BeatriceBatch* b, BeatriceBatch::ResidentBlocks& nr) {
+  const size_t rows = (size_t)nr.io_slots * b->B * nr.H;
+  const bool ok = nr.d_in16.alloc(rows * B_IN_HOP, "rb in16") && nr.d_out24.alloc(rows * B_OUT_HOP, "rb out24") &&
+                  nr.gains.alloc(nr.ring, 2 * (size_t)b->B, "rb gains") && hip_ok(hipDeviceSynchronize(), "rb sync") &&
+                  bind_io(b, nr.d_in16, nr.d_out24, nr.io_slots) == 0 && tick_enable(b, true) == 0;
+  if (!ok) {
+    (void)tick_enable(b, false);
+    (void)bind_io(b, nullptr, nullptr, 0);
+    return false;
+  }
+  b->rb = std::move(nr);
+  return true;
 }
 // leaves either form of the resident blocks: the pipeline drained, tick mode off, the wrapper restarted at its rate(s)
 static int rb_unbind(BeatriceBatch* b) {
@@ -516,7 +510,7 @@ static int rb_unbind(BeatriceBatch* b) {
   if (rc) return rc;
   (void)bind_io(b, nullptr, nullptr, 0);
   const bool ragged = r.ragged;
-  rb_release(b);
+  r = {};
   if (ragged) {
     b->silent.on = false;   // (the flags of the ragged steps were the binding's own)
     std::vector<double> rates(b->B);
@@ -552,8 +546,8 @@ static bool rb_step(BeatriceBatch* b, const bool synthetic) {
   const int ge = (int)(call % r.ring);
   // this call's gain segments: input half now, output half when its job runs.  The kernels read them where they are written (pinned
   // memory): the entry is free again once the output half that read it last has run
-  if (r.ev_recorded[ge]) { if (!hip_ok(hipEventSynchronize(r.gain_ev[ge]), "wrapper gain ring")) return false; r.ev_recorded[ge] = 0; }
-  GainSeg* seg = r.h_gains + (size_t)ge * 2 * B;
+  GainSeg* seg = r.gains.claim(ge);
+  if (!seg) return false;
   for (int s = 0; s < B; ++s) { seg[s] = b->gain_in[s].advance(n, w.rate); seg[B + s] = b->gain_out[s].advance(n, w.rate); }
   const size_t nt = w.taps_down.size();
   WrapCallArgs a{};
@@ -562,7 +556,7 @@ static bool rb_step(BeatriceBatch* b, const bool synthetic) {
   if (m < 0 || m > kMaxSamples) return false;
   const Dir dout = w.to_outer(m);
   if (dout.n_out != n) return false;
-  a.src = synthetic ? r.d_zero : r.d_in + (size_t)(call % r.n_slots) * B * r.channels * n;
+  a.src = synthetic ? r.d_zero.get() : r.d_in + (size_t)(call % r.n_slots) * B * r.channels * n;
   a.channels = r.channels; a.n = n; a.st = b->d_wrap; a.gain_in = seg; a.taps_in = b->d_wrap_taps + (a.din.decimate ? 0 : nt);
   a.inner = b->d_wrap_inner; a.stride = kInnerStride; a.in16 = r.d_in16; a.row16 = H * B_IN_HOP; a.B = B; a.H = H;
   // the 480-sample accumulation; a model hop every time it fills (the per-stream FIFO array holds it), into its place: hop
@@ -591,14 +585,13 @@ static bool rb_step(BeatriceBatch* b, const bool synthetic) {
   int due_ge = -1;
   if (due) {
     due_ge = (int)(due->call % r.ring);
-    a.n_post = B; a.out24 = r.d_out24; a.io_slots = r.io_slots; a.t0 = due->t0; a.gain_out = r.h_gains + (size_t)due_ge * 2 * B + B;
+    a.n_post = B; a.out24 = r.d_out24; a.io_slots = r.io_slots; a.t0 = due->t0; a.gain_out = r.gains.host(due_ge) + B;
     a.taps_out = b->d_wrap_taps + (due->dout.decimate ? 0 : nt); a.dout = due->dout;
     a.out = r.d_out + (size_t)(due->call % r.n_slots) * B * r.channels * n;
   }
   hipLaunchKernelGGL(wrap_call_kernel, dim3(B + a.n_post), dim3(256), 0, st, a);
   if (due) {
-    if (!hip_ok(hipEventRecord(r.gain_ev[due_ge], st), "wrapper gain event")) return false;
-    r.ev_recorded[due_ge] = 1;
+    if (!r.gains.mark(due_ge, st)) return false;
     r.jobs.pop_front();
   }
   // (never more than one call comes due per call under the bind-time bound; should the queue have fallen behind, the rest follow here)
@@ -641,32 +634,15 @@ int BeatriceBatch_BindResidentBlocks(BeatriceBatch* b, const float* d_in, float*
   // binding restarts the resampler pair and the FIFO (their in-order form keeps processed samples in the FIFO, this one does not)
   if (BeatriceBatch_ConfigureWrapper(b, b->wrap.rate) != 0) return -2;
   // model hops a call can fire: ceil(inner samples / 480) + 1; a hop's resident output is read until `delay` calls after the
-  // call in which the NEXT hop fired
   // call in which the NEXT hop fired.  With H hops per step a slot holds a step: the hops of (delay + 2) calls are that many / H steps.
   const int m_max = (int)std::ceil(n * 48000.0 / b->wrap.rate) + 2, hops_per_call = (m_max + wrapn::kBlock - 1) / wrapn::kBlock + 1;
-  r.delay = delay;
-  r.ring = r.delay + 3;
-  r.H = H;
-  r.io_slots = std::max(stages + 1, H == 1 ? (r.delay + 2) * hops_per_call + 2 : ((r.delay + 2) * hops_per_call + H - 1) / H + 3);
-  if (r.io_slots > stepc::kImmediateMaxSlot + 1) { r = BeatriceBatch::ResidentBlocks{}; return -1; }   // (tick mode's limit on resident slots)
-  const int B = b->B;
-  bool ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_in16), sizeof(float) * r.io_slots * B * H * B_IN_HOP), "rb in16") &&
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_out24), sizeof(float) * r.io_slots * B * H * B_OUT_HOP), "rb out24") &&
-            hip_ok(hipMemset(r.d_in16, 0, sizeof(float) * r.io_slots * B * H * B_IN_HOP), "rb zero") &&
-            hip_ok(hipMemset(r.d_out24, 0, sizeof(float) * r.io_slots * B * H * B_OUT_HOP), "rb zero") &&
-            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&r.h_gains), sizeof(wrapn::GainSeg) * r.ring * 2 * B, hipHostMallocDefault), "rb gains host");
-  if (ok) {
-    r.gain_ev = new hipEvent_t[r.ring]();
-    for (int i = 0; i < r.ring && ok; ++i) ok = hip_ok(hipEventCreateWithFlags(&r.gain_ev[i], hipEventDisableTiming), "rb event");
-    r.ev_recorded.assign(r.ring, 0);
-  }
-  ok = ok && hip_ok(hipDeviceSynchronize(), "rb sync") && bind_io(b, r.d_in16, r.d_out24, r.io_slots) == 0 && tick_enable(b, true) == 0;
-  if (!ok) {
-    (void)tick_enable(b, false);
-    (void)bind_io(b, nullptr, nullptr, 0);
-    rb_release(b);
-    return -2;
-  }
+  BeatriceBatch::ResidentBlocks nr;
+  nr.delay = delay;
+  nr.ring = nr.delay + 3;
+  nr.H = H;
+  nr.io_slots = std::max(stages + 1, H == 1 ? (nr.delay + 2) * hops_per_call + 2 : ((nr.delay + 2) * hops_per_call + H - 1) / H + 3);
+  if (nr.io_slots > stepc::kImmediateMaxSlot + 1) return -1;   // (tick mode's limit on resident slots)
+  if (!rb_bind(b, nr)) return -2;
   r.d_in = d_in; r.d_out = d_out; r.channels = channels; r.n = n; r.n_slots = n_slots; r.on = true;
   return 0;
 }
@@ -691,9 +667,9 @@ static int rbr_step(BeatriceBatch* b, const int* n_samples) {
   const int ge = (int)(call % r.ring);
   // (records and gain segments are read by the kernels where they are written, pinned memory: the ring entry is free again once the
   //  output half that read it last has run)
-  if (r.ev_recorded[ge]) { if (!hip_ok(hipEventSynchronize(r.gain_ev[ge]), "wrapper record ring")) return -2; r.ev_recorded[ge] = 0; }
+  GainSeg* seg = r.gains.claim(ge);
+  if (!seg) return -2;
   RagStream* rs = r.h_rs + (size_t)ge * B;
-  GainSeg* seg = r.h_gains + (size_t)ge * 2 * B;
   // all or nothing, as BeatriceBatch_ProcessBlocksRagged: a plan that does not fit puts every clock of the call back
   rw.clk_undo = rw.clk;
   rw.gain_undo_in.assign(b->gain_in.begin(), b->gain_in.end());
@@ -791,32 +767,14 @@ int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, 
     const int m_max = (int)std::ceil(std::min(max_samples, lim) * 48000.0 / rates[s]) + 2;
     hops_per_call = std::max(hops_per_call, (m_max + wrapn::kBlock - 1) / wrapn::kBlock + 1);
   }
-  r.delay = stages - 1;
-  r.ring = r.delay + 3;
-  r.H = 1;
-  r.io_slots = std::max(stages + 1, (r.delay + 2) * hops_per_call + 2);
-  if (r.io_slots > stepc::kImmediateMaxSlot + 1) { r = BeatriceBatch::ResidentBlocks{}; return -1; }
-  r.map_ring = r.io_slots;
-  bool ok = hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_in16), sizeof(float) * r.io_slots * B * B_IN_HOP), "rb in16") &&
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_out24), sizeof(float) * r.io_slots * B * B_OUT_HOP), "rb out24") &&
-            hip_ok(hipMemset(r.d_in16, 0, sizeof(float) * r.io_slots * B * B_IN_HOP), "rb zero") &&
-            hip_ok(hipMemset(r.d_out24, 0, sizeof(float) * r.io_slots * B * B_OUT_HOP), "rb zero") &&
-            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&r.h_gains), sizeof(wrapn::GainSeg) * r.ring * 2 * B, hipHostMallocDefault), "rb gains host") &&
-            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&r.h_rs), sizeof(wrapn::RagStream) * r.ring * B, hipHostMallocDefault), "rb records host") &&
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_map), sizeof(int) * B * r.map_ring), "rb slot map") &&
-            hip_ok(hipMemset(r.d_map, 0, sizeof(int) * B * r.map_ring), "rb slot map zero");
-  if (ok) {
-    r.gain_ev = new hipEvent_t[r.ring]();
-    for (int i = 0; i < r.ring && ok; ++i) ok = hip_ok(hipEventCreateWithFlags(&r.gain_ev[i], hipEventDisableTiming), "rb event");
-    r.ev_recorded.assign(r.ring, 0);
-  }
-  ok = ok && hip_ok(hipDeviceSynchronize(), "rb sync") && bind_io(b, r.d_in16, r.d_out24, r.io_slots) == 0 && tick_enable(b, true) == 0;
-  if (!ok) {
-    (void)tick_enable(b, false);
-    (void)bind_io(b, nullptr, nullptr, 0);
-    rb_release(b);
-    return -2;
-  }
+  BeatriceBatch::ResidentBlocks nr;
+  nr.delay = stages - 1;
+  nr.ring = nr.delay + 3;
+  nr.H = 1;
+  nr.io_slots = std::max(stages + 1, (nr.delay + 2) * hops_per_call + 2);
+  if (nr.io_slots > stepc::kImmediateMaxSlot + 1) return -1;
+  nr.map_ring = nr.io_slots;
+  if (!nr.h_rs.alloc((size_t)nr.ring * B, "rb records host") || !nr.d_map.alloc((size_t)B * nr.map_ring, "rb slot map") || !rb_bind(b, nr)) return -2;
   b->silent.next.assign(B, 0);   // the ragged steps' flags (tick_run): set per tick by rbr_step, not by the caller
   b->silent.any_next = false;
   b->silent.on = true;
@@ -838,10 +796,7 @@ int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b) {
   if (!sync_all(b)) return -2;           // (one hop per step and clocks per stream: everything is out now)
   if (r.jobs.empty()) return 0;
   if (r.ragged || r.H == 1) return -2;   // (cannot be: nothing stays owed there)
-  if (!r.d_zero) {
-    const size_t bytes = sizeof(float) * b->B * r.channels * r.n;
-    if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d_zero), bytes), "rb zeros") || !hip_ok(hipMemset(r.d_zero, 0, bytes), "rb zeros")) return -2;
-  }
+  if (!r.d_zero && !r.d_zero.alloc((size_t)b->B * r.channels * r.n, "rb zeros")) return -2;
   for (int guard = 0; !r.jobs.empty() && guard < 64 * r.H; ++guard) {
     const long long fed = r.hops_fed();
     if (!hip_ok(hipStreamSynchronize(b->stream), "flush sync") || !rb_step(b, true)) { r.dead = true; return -2; }   // (the made-up calls share one gain ring entry: one at a time)
@@ -854,7 +809,7 @@ int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b) {
   r.on = true;
   if (rc != 0) { r.dead = true; return -2; }
   r.calls = 0; r.t48 = 0; r.hops_fired = 0; r.hops_done = 0;
-  std::fill(r.ev_recorded.begin(), r.ev_recorded.end(), 0);
+  r.gains.forget();
   b->io_host = 0;   // (hop k of the binding rides in resident slot (k / H) mod io_slots: wrap_post_kernel)
   return 0;
 }

@@ -23,10 +23,14 @@ LaunchHook*& launch_hook() {
   return hook;
 }
 
-bool DeviceBlob::upload(const float* host, size_t n) {
+bool DeviceBlob::alloc(size_t n) {
   release();
   BHIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), n * sizeof(float)));
   n_floats = n;
+  return true;
+}
+bool DeviceBlob::upload(const float* host, size_t n) {
+  if (!alloc(n)) return false;
   BHIP_TRY(hipMemcpy(d, host, n * sizeof(float), hipMemcpyHostToDevice));
   BHIP_TRY(hipDeviceSynchronize());
   return true;

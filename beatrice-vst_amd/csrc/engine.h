@@ -14,14 +14,14 @@
 #include <cstddef>
 #include <vector>
 
+#include "hip_owned.h"
 #include "kernels_misc.hip.h"
 #include "meas_env.h"
 #include "ring.h"
 
 namespace bhip {
 
-// ---- error handling: never throw across the C-ABI; remember the first failure ---------------
-bool hip_ok(hipError_t e, const char* what);  // logs once per site when BEATRICE_HIP_DEBUG is set
+// ---- error handling: never throw across the C-ABI; remember the first failure (hip_ok: hip_owned.h)
 #define BHIP_TRY(expr)                                \
   do {                                                \
     if (!::bhip::hip_ok((expr), #expr)) return false; \
@@ -47,6 +47,7 @@ inline void launch_site(const LaunchInfo& info, hipStream_t stream, F&& fn) {
 struct DeviceBlob {
   float* d = nullptr;
   size_t n_floats = 0;
+  bool alloc(size_t n);  // uninitialised room for n floats (filled device to device: BeatriceHip_ModelBlob)
   bool upload(const float* host, size_t n);
   void release();
 };

@@ -27,6 +27,7 @@
 
 #include "chain_layers.hip.h"
 #include "fuse.hip.h"
+#include "hip_owned.h"
 #include "rowchain.hip.h"
 #include "tail_stages.hip.h"
 
@@ -187,34 +188,29 @@ struct Consumer {  // a kernel that reads per-stream settings: its private copy 
 
 struct State {
   bool on = false;
-  void* d_table = nullptr;           // Ops<H>::Tab on the device
+  DevBuf<unsigned char> d_table;         // Ops<H>::Tab on the device
   int table_total = 0;
-  void* d_table_sparse = nullptr;    // the same stages with the long bodies in half-size pieces (fill and drain ticks)
+  DevBuf<unsigned char> d_table_sparse;  // the same stages with the long bodies in half-size pieces (fill and drain ticks)
   int table_sparse_total = 0;
   double table_flops = 0, table_bytes = 0;  // algorithmic work of one full tick (sum over the bodies)
-  fuse::WgDesc* d_desc = nullptr;    // dispatch order of the full / the sparse table by workgroup (tick_build_table_h)
-  fuse::WgDesc* d_desc_sparse = nullptr;
-  size_t desc_cap = 0, desc_sparse_cap = 0;
+  DevBuf<fuse::WgDesc> d_desc;       // dispatch order of the full / the sparse table by workgroup (tick_build_table_h)
+  DevBuf<fuse::WgDesc> d_desc_sparse;
   // the full table's workgroups in plain span order (every body on all eight XCDs): the order of PARTLY FILLED ticks -- with few stages
   // occupied a body confined to half the chip leaves the other half idle (a 20-step run: 3.78 -> 3.51 M frames/s with the halves everywhere)
-  fuse::WgDesc* d_desc_plain = nullptr;
-  size_t desc_plain_cap = 0;
+  DevBuf<fuse::WgDesc> d_desc_plain;
   int table_total_plain = 0;
   // ... and the same order with the workgroups of EMPTY stages left out, for the two shapes a fill and a drain go through: stages
   // 0 .. k occupied (range_off[0][k]) and stages k .. last occupied (range_off[1][k]).  A partly filled launch otherwise dispatches
   // every stage's workgroups only for most of them to leave at once -- thousands of slot turns per launch in a run of few steps.
   // One buffer; n = 0: not built (very large batches) or the tick's occupied stages are no such range -> the plain list.
-  fuse::WgDesc* d_desc_ranges = nullptr;
-  size_t desc_ranges_cap = 0;
+  DevBuf<fuse::WgDesc> d_desc_ranges;
   size_t range_off[2][kMaxStages] = {};
   int range_n[2][kMaxStages] = {};
-  unsigned long long* d_trace = nullptr;  // BEATRICE_HIP_TICK_TRACE=<file>: per-workgroup timeline of the last full tick
+  DevBuf<unsigned long long> d_trace;     // BEATRICE_HIP_TICK_TRACE=<file>: per-workgroup timeline of the last full tick
   bool table_dirty = true;
-  unsigned char* d_snap = nullptr;  // [kRing][snap_bytes] settings snapshots
+  DevBuf<unsigned char> d_snap;     // [kRing][snap_bytes] settings snapshots
   static constexpr int kStaging = 16;
-  unsigned char* h_stage = nullptr; // [kStaging][snap_bytes] pinned: a snapshot on its way to the device
-  hipEvent_t stage_ev[kStaging] = {};
-  bool stage_pending[kStaging] = {};
+  StagedRing<unsigned char> stage;  // [kStaging][snap_bytes]: a snapshot on its way to the device
   size_t snap_bytes = 0;
   long long tick = 0, n_fed = 0, last_feed_tick = -1000;
   long long fed_step[kRing];        // step fed at tick (index tick % kRing), -1 none
@@ -228,19 +224,17 @@ struct State {
   bool ragged = false;
   int row = 0;                        // ints per step (B rounded up to a multiple of 4: the prologue copies 16-byte pieces)
   std::vector<int> hop_s;             // [B] the streams' counters on the host
-  int* d_hopv = nullptr;              // [kRing][row]
-  int* h_hopv = nullptr;              // [kStaging][row] pinned
-  hipEvent_t hv_ev[kStaging] = {};
-  bool hv_pending[kStaging] = {};
+  DevBuf<int> d_hopv;                 // [kRing][row]
+  StagedRing<int> hopv;               // [kStaging][row]: a step's counters on their way to the device
   bool step_ragged[kRing] = {};       // step u (at [u % kRing]) carries per-stream counters
   // back to one counter at a drained point (batch_tick.hip.h tick_relevel): the table of the batch's rings, the streams' deficits
-  void* d_ring_table = nullptr;       // FreezeRing [n_ring_table]
+  DevBuf<FreezeRing> d_ring_table;    // [n_ring_table]
   int n_ring_table = 0;
-  int* d_shift = nullptr;             // [B]
+  DevBuf<int> d_shift;                // [B]
   // several hops per step: the granules that link the GRU cells of a step's hops inside a launch (fused_small.hip.h GruArgs::link_*)
-  unsigned long long* d_link_q = nullptr;   // [H - 1][B][128]: link t = hop t's state for hop t + 1
-  unsigned long long* d_link_p = nullptr;   // [H - 1][B][256]
-  int* h_link_dead = nullptr;               // pinned: a cell gave a wait up
+  DevBuf<unsigned long long> d_link_q;      // [H - 1][B][128]: link t = hop t's state for hop t + 1
+  DevBuf<unsigned long long> d_link_p;      // [H - 1][B][256]
+  PinnedBuf<int> h_link_dead;               // a cell gave a wait up
 };
 
 }  // namespace tick

@@ -111,6 +111,124 @@ def test_wrapper_bindings_around_the_ticks_do_not_leak(bv, product, model_dir):
     assert before - after <= 8 << 20
 
 
+def test_every_other_mode_does_not_leak(bv, product, model_dir):
+    """The owners the tests above do not reach: stage streams (EnablePipelining(3)), host streaming, the 48 kHz wrapper around the ticks,
+    the silent-block rule in order with a flagged block, tick mode with streams that sit steps out (the per-stream counters), the
+    per-stream-clock wrapper in order, and FlushResidentBlocks at two hops per step (its block of zeros).  One cycle = every mode once;
+    every other batch of a mode is destroyed while still in it."""
+    import ctypes as C
+    from tick_driver import Hip
+    m = bv.Models(product, model_dir)
+    hip = Hip()
+    B = 8
+
+    def stage_streams(batch, leave):
+        assert batch.a.BeatriceBatch_EnablePipelining(batch.h, 3) == 0
+        x = np.zeros((B, 160), np.float32)
+        batch.convert(x)
+        batch.convert(x)
+        if leave:
+            assert batch.a.BeatriceBatch_EnablePipelining(batch.h, 0) == 0
+
+    def host_streaming(batch, leave):
+        a, h = batch.a, batch.h
+        assert a.BeatriceBatch_EnableHostStreaming(h, 1) == 0
+        x, out = np.zeros((B, 160), np.float32), np.zeros((B, 240), np.float32)
+        for _ in range(a.BeatriceBatch_HostStreamDelay(h) + 4):
+            assert a.BeatriceBatch_StreamFrames(h, bv.fptr(x), bv.fptr(out)) in (0, 1)
+        if leave:
+            while a.BeatriceBatch_StreamFlush(h, bv.fptr(out)) == 1:
+                pass
+            assert a.BeatriceBatch_EnableHostStreaming(h, 0) == 0
+
+    def resident_48k(batch, leave):
+        a, h = batch.a, batch.h
+        slots = a.BeatriceBatch_TickStages(h) + 2
+        nbytes = slots * B * 480 * 4
+        d_in, d_out = hip.malloc(nbytes), hip.malloc(nbytes)
+        assert hip.lib.hipMemset(d_in, 0, C.c_size_t(nbytes)) == 0
+        assert a.BeatriceBatch_BindResidentIO48k(h, d_in, d_out, 1, slots) == 0
+        for _ in range(6):
+            assert a.BeatriceBatch_ConvertBlocks48kDevice(h, None, None, 1) == 0
+        assert a.BeatriceBatch_Synchronize(h) == 0
+        if leave:
+            assert a.BeatriceBatch_BindResidentIO48k(h, None, None, 0, 0) == 0
+        return d_in, d_out
+
+    def silent_rule_in_order(batch, leave):
+        a, h = batch.a, batch.h
+        assert a.BeatriceBatch_EnableSilentBlockRule(h, 1) == 0
+        x = np.full((B, 1, 480), 0.25, np.float32)
+        x[0] = 0.0   # stream 0's block is silent by the shell's rule
+        for _ in range(3):
+            batch.convert48k(x, 1)
+        if leave:
+            assert a.BeatriceBatch_EnableSilentBlockRule(h, 0) == 0
+
+    def ticks_with_streams_sitting_out(batch, leave):
+        a, h = batch.a, batch.h
+        slots = a.BeatriceBatch_TickStages(h) + 2
+        d_in, d_out = hip.malloc(slots * B * 160 * 4), hip.malloc(slots * B * 240 * 4)
+        assert hip.lib.hipMemset(d_in, 0, C.c_size_t(slots * B * 160 * 4)) == 0
+        assert a.BeatriceBatch_BindResidentIO(h, d_in, d_out, slots) == 0
+        assert a.BeatriceBatch_EnableTickPipeline(h, 1) == 0
+        assert a.BeatriceBatch_EnableSilentBlockRule(h, 1) == 0
+        for k in range(6):
+            assert a.BeatriceBatch_SetSilentStreams(h, bytes([1 if s == k % B else 0 for s in range(B)])) == 0
+            assert a.BeatriceBatch_ConvertFramesDevice(h, None, None) == 0
+        assert a.BeatriceBatch_Synchronize(h) == 0
+        if leave:
+            assert a.BeatriceBatch_EnableTickPipeline(h, 0) == 0
+            assert a.BeatriceBatch_BindResidentIO(h, None, None, 0) == 0
+        return d_in, d_out
+
+    def per_stream_clocks_in_order(batch, leave):
+        a, h = batch.a, batch.h
+        assert a.BeatriceBatch_ConfigureWrapperRates(h, (C.c_double * B)(*([44100.0, 48000.0] * (B // 2)))) == 0
+        ns = [441, 480] * (B // 2)
+        xin = np.full(sum(ns), 0.25, np.float32)
+        out = np.zeros_like(xin)
+        for _ in range(3):
+            assert a.BeatriceBatch_ProcessBlocksRagged(h, bv.fptr(xin), bv.fptr(out), 1, (C.c_int * B)(*ns), 0) == 0
+
+    def flush_at_two_hops(batch, leave):
+        a, h = batch.a, batch.h
+        block = 441
+        assert a.BeatriceBatch_ConfigureWrapper(h, 44100.0) == 0
+        slots = a.BeatriceBatch_ResidentBlocksDelayFor(h, block) + 4
+        d_in, d_out = hip.malloc(slots * B * 480 * 4), hip.malloc(slots * B * 480 * 4)
+        assert hip.lib.hipMemset(d_in, 0, C.c_size_t(slots * B * 480 * 4)) == 0
+        assert a.BeatriceBatch_BindResidentBlocks(h, d_in, d_out, 1, block, slots) == 0
+        for _ in range(5):
+            assert a.BeatriceBatch_ProcessBlocksDevice(h, None, None, 1, block) == 0
+        assert a.BeatriceBatch_FlushResidentBlocks(h) == 0
+        assert a.BeatriceBatch_ResidentBlocksOwed(h) == 0
+        if leave:
+            assert a.BeatriceBatch_BindResidentBlocks(h, None, None, 0, 0, 0) == 0
+        return d_in, d_out
+
+    kinds = [(stage_streams, 1), (host_streaming, 1), (resident_48k, 1), (silent_rule_in_order, 1), (ticks_with_streams_sitting_out, 1),
+             (per_stream_clocks_in_order, 1), (flush_at_two_hops, 2)]
+
+    def cycle(i):
+        for j, (run, H) in enumerate(kinds):
+            batch = bv.Batch(m, B, hops_per_step=H)
+            mine = run(batch, (i + j) % 2 == 0)
+            batch.close()
+            for p in mine or ():
+                hip.free(p)
+
+    for i in range(4):
+        cycle(i)
+    before = _free_bytes()
+    for i in range(8):
+        cycle(i)
+    after = _free_bytes()
+    m.close()
+    print("free device memory: %.1f MB -> %.1f MB" % (before / 2**20, after / 2**20))
+    assert before - after <= 8 << 20
+
+
 def test_unhealthy_objects_fail_softly(bv, product, model_dir):
     """Calls on objects that could not be built must not crash: error code from the batch, zeros from the
     void per-hop calls ('Errors')."""
