@@ -40,6 +40,15 @@ class _Calls:
             c["s1"].set_target_speaker(speaker)   # codebook + additive now, K/V registered: blocks follow one per hop
         return self._each(stream, f)
 
+    def BeatriceBatch_SetTargetSpeakers(self, h, n, streams, speakers):
+        # n (stream, speaker) pairs, all or nothing (include/beatrice_batch.h): the same as n calls of SetTargetSpeaker
+        pairs = [(int(streams[i]), int(speakers[i])) for i in range(n)]
+        if any(not 0 <= s < self.o.B or sp < 0 for s, sp in pairs):
+            return -1
+        for s, sp in pairs:
+            self.BeatriceBatch_SetTargetSpeaker(h, s, sp)
+        return 0
+
     def BeatriceBatch_FlushSpeaker(self, h, stream):
         def f(c):
             while c["s1"].set_kv_block():
@@ -108,17 +117,20 @@ class _Calls:
 
 
 class OracleBatch:
-    def __init__(self, bv, oracle_abi, model_dir, n_streams, sample=None, models=None):
+    calls_class = _Calls
+
+    def __init__(self, bv, oracle_abi, model_dir, n_streams, sample=None, models=None, hops_per_step=1):
         self.bv = bv
         self.B = n_streams
+        self.H = hops_per_step
         self.sample = sorted(set(range(n_streams) if sample is None else [s for s in sample if 0 <= s < n_streams]))
         self._own_models = models is None
         self.m = models if models is not None else bv.Models(oracle_abi, model_dir)
         self.h = None
-        self.a = _Calls(self)
+        self.a = self.calls_class(self)
         self.st = {}
         for s in self.sample:
-            c = dict(speaker=0, formant=4, vq_k=0, min_q=1, max_q=bv.PITCH_BINS - 1, pitch={}, s1=None)
+            c = dict(speaker=0, formant=4, vq_k=0, min_q=1, max_q=bv.PITCH_BINS - 1, pitch={}, s1=None, absent=False)
             self.st[s] = c
             self._fresh(c, first=True)
         # bv.Batch.apply_defaults: speaker 0 with every K/V block installed, default pitch search range
@@ -132,12 +144,33 @@ class OracleBatch:
         c["s1"] = self.bv.Stream1(self.m, speaker=c["speaker"], formant_index=c["formant"], vq_k=c["vq_k"], min_q=c["min_q"], max_q=c["max_q"])
         c["s1"].pitch_params = dict(c["pitch"])
 
-    def convert(self, x):
-        """x: [B][160] (rows of non-sampled streams are ignored) -> {stream: [240]} for the sampled streams."""
-        return {s: self.st[s]["s1"].hop(x[s]) for s in self.sample}
+    def step_stream(self, s, xs):
+        """One step of sampled stream s: its H hops one after the other, xs [H * 160] -> [H * 240]."""
+        s1 = self.st[s]["s1"]
+        return np.concatenate([s1.hop(xs[hh * 160:(hh + 1) * 160]) for hh in range(self.H)])
+
+    def begin_step(self, s, absent):
+        """Told before the events of a step: whether sampled stream s will sit the step out (nothing here depends on it: a setting made
+        while a stream is absent is kept and waits; the deliberately wrong variants of tests/test_cpu_scenarios.py hook in here)."""
+        self.st[s]["absent"] = bool(absent)
+
+    def sit_out(self, s):
+        """Stream s sits this step out: the shell does not call the core for a silent block (reference src/vst/processor.cc:204-214),
+        so its H hops are never made -- state, pending key/value installs and settings wait."""
+
+    def convert(self, x, absent=()):
+        """x: [B][H * 160] (rows of non-sampled streams are ignored) -> {stream: [H * 240]} for the sampled streams that take
+        part in the step; the streams in `absent` sit it out and have no entry."""
+        out = {}
+        for s in self.sample:
+            if s in absent:
+                self.sit_out(s)
+            else:
+                out[s] = self.step_stream(s, x[s])
+        return out
 
     def convert_rows(self, x):
-        """The sampled streams' samples as an array [len(sample)][240], in the order of `self.sample`."""
+        """The sampled streams' samples as an array [len(sample)][H * 240], in the order of `self.sample`."""
         out = self.convert(x)
         return np.stack([out[s] for s in self.sample])
 

@@ -39,26 +39,23 @@ def test_streams_that_sit_steps_out_in_tick_mode_match_the_oracle(bv, oracle, pr
 
     # ---- reference: one oracle stream per sampled stream (tests/oracle_batch.py: the batch's defaults and setters on independent
     # Stream1 objects); a step a stream sits out is a hop that is never made
-    ob = OracleBatch(bv, oracle, model_dir, B, sample=sample)
+    ob = OracleBatch(bv, oracle, model_dir, B, sample=sample, hops_per_step=H)
     for s in range(B):
         ob.a.BeatriceBatch_SetTargetSpeaker(None, s, s % 3)
         ob.a.BeatriceBatch_SetVQNumNeighbors(None, s, s % 3)
     ob.a.BeatriceBatch_FlushSpeaker(None, -1)
-    def oracle_step(s, xs):   # the step's H hops of one stream, one after the other
-        return np.concatenate([ob.st[s]["s1"].hop(xs[hh * 160:(hh + 1) * 160]) for hh in range(H)])
-
     want = np.zeros((steps, B, H * 240), np.float32)
     for k in range(steps):
         for s in ob.sample:
             if s in switch and switch[s][0] == k:
                 ob.a.BeatriceBatch_SetTargetSpeaker(None, s, switch[s][1])
-            if k not in out[s]:
-                want[k, s] = oracle_step(s, x[s, k])
+        for s, y in ob.convert(x[:, k], absent={s for s in ob.sample if k in out[s]}).items():   # (OracleBatch.sit_out: the hops are not made)
+            want[k, s] = y
     sample = ob.sample
     want_tail = np.zeros((tail, B, H * 240), np.float32)
     for k in range(tail):
-        for s in sample:
-            want_tail[k, s] = oracle_step(s, x[s, steps + k])
+        for s, y in ob.convert(x[:, steps + k]).items():
+            want_tail[k, s] = y
     ob.close()
 
     # ---- product: tick mode, flags name the streams that sit the next step out

@@ -24,6 +24,60 @@ class Hip:
         self.lib.hipFree(p)
 
 
+class Resident:
+    """Resident I/O slots bound to a batch for as long as the object lives, so that a caller can feed a run chunk by chunk and keep the
+    binding (and the slot counter: step j since the binding <-> slot j mod slots) between the chunks.  tick=True turns tick mode on
+    over the binding, False leaves it at plain resident I/O."""
+
+    def __init__(self, bv, batch, slots=None, tick=True):
+        self.hip, self.batch, self.tick = Hip(), batch, tick
+        a, h, B, H = batch.a, batch.h, batch.B, batch.H
+        self.slots = slots or a.BeatriceBatch_TickStages(h) + 6
+        self.d_in, self.d_out = self.hip.malloc(self.slots * B * H * 160 * 4), self.hip.malloc(self.slots * B * H * 240 * 4)
+        self.fed = 0
+        try:
+            assert a.BeatriceBatch_BindResidentIO(h, self.d_in, self.d_out, self.slots) == 0
+            if tick:
+                assert a.BeatriceBatch_EnableTickPipeline(h, 1) == 0
+        except BaseException:
+            self.free()
+            raise
+        self.buf = np.zeros((self.slots, B, H * 160), np.float32)
+
+    def feed(self, inputs, before_step=None):
+        """Feeds len(inputs) (<= slots) steps without waiting, drains, and returns their samples [n][B][H * 240].
+        before_step(j) runs before the j-th step of this call is fed (settings travel with the step)."""
+        a, h, B, H, slots = self.batch.a, self.batch.h, self.batch.B, self.batch.H, self.slots
+        n = len(inputs)
+        assert n <= slots
+        for j in range(n):
+            self.buf[(self.fed + j) % slots] = inputs[j]
+        self.hip.h2d(self.d_in, self.buf)
+        for j in range(n):
+            if before_step is not None:
+                before_step(j)
+            assert a.BeatriceBatch_ConvertFramesDevice(h, None, None) == 0
+        assert a.BeatriceBatch_Synchronize(h) == 0
+        out = np.zeros((slots, B, H * 240), np.float32)
+        self.hip.d2h(out, self.d_out)
+        got = np.stack([out[(self.fed + j) % slots] for j in range(n)]) if n else np.zeros((0, B, H * 240), np.float32)
+        self.fed += n
+        return got
+
+    def leave(self):
+        """Back to the in-order chain (streams that have sat steps out come back to the batch's step counter at every drained point)."""
+        a, h = self.batch.a, self.batch.h
+        if self.tick:
+            assert a.BeatriceBatch_EnableTickPipeline(h, 0) == 0
+        assert a.BeatriceBatch_BindResidentIO(h, None, None, 0) == 0
+
+    def free(self):
+        if self.d_in is not None:
+            self.hip.free(self.d_in)
+            self.hip.free(self.d_out)
+            self.d_in = self.d_out = None
+
+
 def run_tick(bv, batch, steps, hop_input, change=None, slots=None, chunk=None, leave=True):
     """Feeds `steps` steps through tick mode and returns their samples [steps][B][H * 240] (H = the batch's hops per step).
 
@@ -31,37 +85,18 @@ def run_tick(bv, batch, steps, hop_input, change=None, slots=None, chunk=None, l
     The resident I/O has `slots` slots (default: stages + 6) used round-robin as the library does (step k <-> slot k mod
     slots); steps are fed `chunk` (<= slots) at a time without waiting, then the pipeline is drained and the chunk read back,
     so the ring wraps many times over a long run."""
-    hip = Hip()
-    a, h, B, H = batch.a, batch.h, batch.B, batch.H
-    stages = a.BeatriceBatch_TickStages(h)
-    slots = slots or stages + 6
-    chunk = min(chunk or slots, slots)
-    d_in, d_out = hip.malloc(slots * B * H * 160 * 4), hip.malloc(slots * B * H * 240 * 4)
+    r = Resident(bv, batch, slots=slots, tick=True)
     try:
-        assert a.BeatriceBatch_BindResidentIO(h, d_in, d_out, slots) == 0
-        assert a.BeatriceBatch_EnableTickPipeline(h, 1) == 0
-        got = np.zeros((steps, B, H * 240), np.float32)
-        buf = np.zeros((slots, B, H * 160), np.float32)
+        chunk = min(chunk or r.slots, r.slots)
+        got = np.zeros((steps, batch.B, batch.H * 240), np.float32)
         k0 = 0
         while k0 < steps:
             n = min(chunk, steps - k0)
-            for k in range(k0, k0 + n):
-                buf[k % slots] = hop_input(k)
-            hip.h2d(d_in, buf)
-            for k in range(k0, k0 + n):
-                if change is not None:
-                    change(batch, k)
-                assert a.BeatriceBatch_ConvertFramesDevice(h, None, None) == 0
-            assert a.BeatriceBatch_Synchronize(h) == 0
-            out = np.zeros((slots, B, H * 240), np.float32)
-            hip.d2h(out, d_out)
-            for k in range(k0, k0 + n):
-                got[k] = out[k % slots]
+            got[k0:k0 + n] = r.feed([hop_input(k) for k in range(k0, k0 + n)],
+                                    (lambda j, k0=k0: change(batch, k0 + j)) if change is not None else None)
             k0 += n
-        if leave:   # (streams that have sat steps out come back to the batch's step counter at every drained point)
-            assert a.BeatriceBatch_EnableTickPipeline(h, 0) == 0
-            assert a.BeatriceBatch_BindResidentIO(h, None, None, 0) == 0
+        if leave:
+            r.leave()
     finally:
-        hip.free(d_in)
-        hip.free(d_out)
+        r.free()
     return got
