@@ -417,6 +417,8 @@ _BATCH = {
     "BeatriceBatch_SetPitchCorrection": (C.c_int, [_vp, C.c_int, C.c_double]),
     "BeatriceBatch_SetPitchCorrectionType": (C.c_int, [_vp, C.c_int, C.c_int]),
     "BeatriceBatch_ResetStream": (C.c_int, [_vp, C.c_int]),
+    "BeatriceBatch_ResetStreamInFlight": (C.c_int, [_vp, C.c_int]),
+    "BeatriceBatch_TicksLaunched": (C.c_longlong, [_vp]),
     "BeatriceBatch_ConvertFrames": (C.c_int, [_vp, _f32p, _f32p]),
     "BeatriceBatch_ConvertFramesDevice": (C.c_int, [_vp, _vp, _vp]),
     "BeatriceBatch_ConvertBlocks48k": (C.c_int, [_vp, _f32p, _f32p, C.c_int]),

@@ -1185,6 +1185,20 @@ int BeatriceBatch_ResetStream(BeatriceBatch* b, int stream) {
   if (!ok) return -2;
   return BeatriceBatch_FlushSpeaker(b, stream);
 }
+// The same as a per-stream setting that travels with the next step (beatrice_batch.h; tick_reset.hip.h): in plain tick mode and in host
+// streaming nothing drains -- the stream is marked, its key/value blocks are installed as BeatriceBatch_FlushSpeaker does, and tick_run
+// carries the reset through the stages with the step it applies to.  Every other mode: BeatriceBatch_ResetStream.
+int BeatriceBatch_ResetStreamInFlight(BeatriceBatch* b, int stream) {
+  BATCH_OPEN(b);
+  if (stream < -1 || stream >= b->B) return -1;
+  const modes::Mode mode = modes::mode_of(flags_of(b));
+  if (mode != modes::Mode::D && mode != modes::Mode::E) return BeatriceBatch_ResetStream(b, stream);
+  if (!tick_reset_prepare(b)) return -2;
+  for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? b->B : stream + 1); ++s) b->tk.reset_pending[s] = 1;
+  b->tk.any_reset_pending = true;
+  return BeatriceBatch_FlushSpeaker(b, stream);
+}
+long long BeatriceBatch_TicksLaunched(const BeatriceBatch* b) { return b && b->tk.on ? b->tk.tick : 0; }
 
 // ---- per-hop ------------------------------------------------------------------------------------
 int BeatriceBatch_ConvertFramesDevice(BeatriceBatch* b, const float* d_in, float* d_out) {

@@ -322,6 +322,162 @@ struct HostProf {
     t0 = t1;
   }
 };
+// ---- a stream starts over inside the pipeline (BeatriceBatch_ResetStreamInFlight; the device side and the reasoning: tick_reset.hip.h)
+// The table of what a reset that applies to step k clears, and when: "before stage s" = in front of the launch of tick k + s, `spare`
+// = but for the slot step k itself has written (the ring's producer ran one tick earlier).  Every ring of the three arenas is accounted
+// for here (the count is checked against the arenas):
+//   phone   audio                      before F1 (0), whole          -- written and read, with history, by F1 alone
+//           f[0] .. f[4]               before F2 .. F5, RB0, spare   -- producer at the stage before, one reader with history
+//           rb[0] .. rb[2]             before RB1 .. RB3, spare      -- (a residual block takes its residual from the same ring, same stage)
+//           rb[3], raw                 nothing                       -- read at the step's own frames only (GRU input; k-NN input)
+//           h                          NO WINDOW: cell run again after tick k + PGRU (phone.out reads step k - 1's last frame in the
+//                                      launch in which the cell of step k reads it as its previous state)
+//   pitch   audio                      before FFT (3), whole
+//           spec, p[0], p[1]           before P1, P2, P3, spare
+//           p[2], logits               nothing
+//           h                          NO WINDOW: cell run again after tick k + QGRU (pitch.out, and the head one tick later, read
+//                                      step k - 1's frame: it is put back after the restart)
+//           d_prev_q (no ring)         before HEAD, whole
+//   wave    e                          nothing                       -- (conditioning of the step's own frames)
+//           x[0] .. x[3]               before block i's first half, spare -- written by wave.inp / the block before's second half, read
+//                                                                      with history by the dilated convolution only (the residual is the
+//                                                                      same body); the spare slots of boundary_slots are history nobody reads
+//           x[4]                       before up1, spare
+//           scratch h1, xa, q, sc, o   nothing                       -- xa: the second half reads the step's own frames, the others are unused here
+//           ya1, yb1, yc1              before res1a, res1b, up2, spare
+//           ya2                        before the tail's first stage, spare
+//           tail                       its three parts (YB2 YC2 | YA3 YB3 YC3 | YA4 YB4 YC4) before the tail stage that owns them, whole
+//                                      (one stage with the fused tail: all three before it); the sub-steps' carried frames live in LDS
+//           ya3, ya4                   nothing                       -- their two-frame histories are TS_YA3 / TS_YA4 of the tail block
+static bool tick_reset_prepare(BeatriceBatch* b) {
+  using namespace tick;
+  State& k = b->tk;
+  if ((int)k.reset_pending.size() != b->B) { k.reset_pending.assign(b->B, 0); k.any_reset_pending = false; }
+  if (k.d_reset_rings) return true;
+  const Plan pl = k.plan;
+  const PhoneState& ps = b->phone;
+  const PitchState& qs = b->pitch;
+  const WaveState& ws = b->wave;
+  std::vector<ResetRing> rings;
+  std::vector<int> stage;
+  std::vector<unsigned char> spare;
+  size_t accounted = 0;
+  auto clear = [&](const Ring& r, int before_stage, bool sp) {
+    rings.push_back(ResetRing{r.base, (unsigned)ring_stream_floats(r), (unsigned)(r.n * r.C), r.m});
+    stage.push_back(before_stage); spare.push_back(sp ? 1 : 0); ++accounted;
+  };
+  auto nothing = [&](const Ring& r) { if (r.base) ++accounted; };
+  clear(ps.audio, Plan::F1, false);
+  clear(ps.f[0], Plan::F2, true); clear(ps.f[1], Plan::F3, true); clear(ps.f[2], Plan::F4, true); clear(ps.f[3], Plan::F5, true); clear(ps.f[4], Plan::RB0, true);
+  for (int i = 0; i < 3; ++i) clear(ps.rb[i], Plan::RB0 + i + 1, true);
+  nothing(ps.rb[3]); nothing(ps.raw); nothing(ps.h);   // (h: the restarted cell)
+  clear(qs.audio, Plan::FFT, false);
+  clear(qs.spec, Plan::P1, true); clear(qs.p[0], Plan::P2, true); clear(qs.p[1], Plan::P2 + 1, true);
+  nothing(qs.p[2]); nothing(qs.logits); nothing(qs.h);
+  nothing(ws.e);
+  for (int blk = 0; blk < B_NBLOCKS; ++blk) clear(ws.x[blk], pl.blk(blk), true);
+  clear(ws.x[B_NBLOCKS], pl.up1(), true);
+  for (const WaveState::Scratch& sc : ws.scr) { nothing(sc.h1); nothing(sc.xa); nothing(sc.q); nothing(sc.sc); nothing(sc.o); }
+  clear(ws.ya1, pl.up1() + 1, true); clear(ws.yb1, pl.up1() + 2, true); clear(ws.yc1, pl.up1() + 3, true);
+  clear(ws.ya2, pl.tail(), true);
+  {
+    const int part[4] = {TS_YB2, TS_YA3, TS_YA4, TAIL_STATE_FLOATS};
+    for (int i = 0; i < 3; ++i) {
+      rings.push_back(ResetRing{ws.tail.base + part[i], (unsigned)TAIL_STATE_FLOATS, (unsigned)(part[i + 1] - part[i]), 1});
+      stage.push_back(pl.split_tail ? pl.tail() + i : pl.tail()); spare.push_back(0);
+    }
+    ++accounted;
+  }
+  nothing(ws.ya3); nothing(ws.ya4);
+  rings.push_back(ResetRing{reinterpret_cast<float*>(qs.d_prev_q), 1u, 1u, 1});   // (an int; zero is zero)
+  stage.push_back(Plan::HEAD); spare.push_back(0);
+  if (accounted != ps.arena.rings.size() + qs.arena.rings.size() + ws.arena.rings.size() || ws.tail.C != TAIL_STATE_FLOATS || ws.tail.n * ws.tail.m != 1) {
+    std::fprintf(stderr, "beatrice_hip: the in-flight reset table does not cover the batch's rings\n");
+    return false;
+  }
+  DevBuf<ResetRing> d_rings;
+  DevBuf<float> keep;
+  StagedRing<int> list;
+  // (a tick's list: at most one item per ring and stream -- the resets at one depth of the pipeline are of different streams -- and the
+  //  two cells' {stream, counter} pairs behind them)
+  const size_t list_ints = 4 * rings.size() * (size_t)b->B + 2 * 2 * (size_t)b->B;
+  if (!d_rings.alloc(rings.size(), "reset ring table", false) ||
+      !hip_ok(hipMemcpy(d_rings, rings.data(), sizeof(ResetRing) * rings.size(), hipMemcpyHostToDevice), "reset ring table up") ||
+      !keep.alloc((size_t)b->B * (256 + 128), "reset gru keep", false) || !list.alloc(State::kResetStaging, list_ints, "reset work list"))
+    return false;
+  k.n_reset_rings = (int)rings.size(); k.d_reset_rings = std::move(d_rings); k.reset_stage = std::move(stage); k.reset_spare = std::move(spare);
+  k.reset_m.clear();
+  for (const ResetRing& r : rings) k.reset_m.push_back(r.m);
+  k.d_gru_keep = std::move(keep); k.reset_list = std::move(list); k.reset_list_ints = list_ints;
+  return true;
+}
+// In front of the launch of tick k.tick: what the resets that are travelling need cleared before it, and the cells to run again behind
+// the tick before.  Nothing is launched on a tick that has no such work.
+static bool tick_reset_launch(BeatriceBatch* b, hipStream_t st) {
+  using namespace tick;
+  State& k = b->tk;
+  const int n_stages = k.plan.count(), B = b->B;
+  int n_items = 0, n_p = 0, n_q = 0;
+  int* list = nullptr;
+  auto claim = [&]() {
+    if (!list) list = k.reset_list.claim((int)(k.reset_serial % State::kResetStaging));
+    return list != nullptr;
+  };
+  const size_t off_p = 4 * (size_t)k.n_reset_rings * B, off_q = off_p + 2 * (size_t)B;
+  size_t keep_n = 0;
+  for (const State::Travelling& r : k.resets) {
+    const int d = (int)(k.tick - r.tick);   // the stage the reset's step reaches in this tick
+    if (d < n_stages) k.resets[keep_n++] = r;
+    if (d >= n_stages) continue;
+    for (int i = 0; i < k.n_reset_rings; ++i) {
+      if (k.reset_stage[i] != d) continue;
+      if (!claim()) return false;
+      const ResetItem it{i, r.stream, k.reset_spare[i] ? r.counter % k.reset_m[i] : -1, 0};   // (ring_pos: the slot of the stream's counter)
+      std::memcpy(list + 4 * (size_t)n_items++, &it, sizeof(it));
+    }
+    if (d == Plan::PGRU + 1 || d == Plan::QGRU + 1) {
+      if (!claim()) return false;
+      int* g = d == Plan::PGRU + 1 ? list + off_p + 2 * (size_t)n_p++ : list + off_q + 2 * (size_t)n_q++;
+      g[0] = r.stream; g[1] = r.counter;
+    }
+  }
+  k.resets.resize(keep_n);
+  if (!list) return true;
+  if (n_items > 0)
+    hipLaunchKernelGGL(ring_reset_kernel, dim3(n_items), dim3(256), 0, st, k.d_reset_rings.get(), k.n_reset_rings, reinterpret_cast<const ResetItem*>(list), B);
+  const int H = b->H;
+  if (n_p > 0) {
+    const PhoneWeights& pw = b->phone_m->w;
+    const GruArgs g{b->phone.rb[3], b->phone.h, pw.gru_wih, pw.gru_whh, pw.gru_bih, pw.gru_bhh, nullptr, B, 0, nullptr, nullptr, nullptr, 1};
+    const int2* items = reinterpret_cast<const int2*>(list + off_p);
+    for (int ph = -1; ph <= H; ++ph)
+      hipLaunchKernelGGL((gru_restart_kernel<256, 256>), dim3(n_p, 256 / 16), dim3(384), 0, st, g, items, k.d_gru_keep.get(), ph < 0 ? kGruSave : (ph == H ? kGruRestore : ph));
+  }
+  if (n_q > 0) {
+    const PitchWeights& qw = b->pitch_m->w;
+    const GruArgs g{b->pitch.p[2], b->pitch.h, qw.gru_wih, qw.gru_whh, qw.gru_bih, qw.gru_bhh, nullptr, B, 0, nullptr, nullptr, nullptr, 1};
+    const int2* items = reinterpret_cast<const int2*>(list + off_q);
+    for (int ph = -1; ph <= H; ++ph)
+      hipLaunchKernelGGL((gru_restart_kernel<128, 128>), dim3(n_q, 128 / 16), dim3(384), 0, st, g, items, k.d_gru_keep + (size_t)B * 256, ph < 0 ? kGruSave : (ph == H ? kGruRestore : ph));
+  }
+  if (!k.reset_list.mark((int)(k.reset_serial % State::kResetStaging), st)) return false;
+  k.reset_serial += 1;
+  k.reset_launches += 1;
+  return hip_ok(hipGetLastError(), "in-flight reset");
+}
+// The drained form of a reset for the streams still waiting for their step (leaving tick mode: the in-order chain takes the batch over)
+static bool tick_reset_settle(BeatriceBatch* b) {
+  tick::State& k = b->tk;
+  bool ok = true;
+  for (int s = 0; s < (int)k.reset_pending.size() && ok && k.any_reset_pending; ++s) {
+    if (!k.reset_pending[s]) continue;
+    ok = b->phone.arena.zero_stream(s, b->stream) && b->pitch.arena.zero_stream(s, b->stream) && b->wave.arena.zero_stream(s, b->stream) &&
+         hip_ok(hipMemsetAsync(b->pitch.d_prev_q + s, 0, sizeof(int), b->stream), "prev_q");
+  }
+  std::fill(k.reset_pending.begin(), k.reset_pending.end(), 0);
+  k.any_reset_pending = false;
+  return ok && hip_ok(hipStreamSynchronize(b->stream), "reset settle");
+}
 bool tick_run(BeatriceBatch* b, bool feeding) {
   using namespace tick;
   State& k = b->tk;
@@ -395,6 +551,20 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
       for (int s = b->B; s < k.row; ++s) h[s] = -1;
       hv_upload = Copy{reinterpret_cast<unsigned char*>(k.d_hopv + (size_t)(u % kRing) * k.row), reinterpret_cast<const unsigned char*>(h), (int)(sizeof(int) * k.row)};
       hv_stage = si;
+      if (k.any_reset_pending) {   // a stream starts over at this step (BeatriceBatch_ResetStreamInFlight) -- one that sits it out, at its next present step
+        bool left = false;
+        for (int s = 0; s < b->B; ++s) {
+          if (!k.reset_pending[s]) continue;
+          if (h[s] < 0) { left = true; continue; }
+          k.resets.push_back(State::Travelling{s, h[s], k.tick});
+          k.reset_pending[s] = 0;
+        }
+        k.any_reset_pending = left;
+      }
+    } else if (k.any_reset_pending) {   // (the common counter: every stream takes part)
+      for (int s = 0; s < b->B; ++s)
+        if (k.reset_pending[s]) { k.resets.push_back(State::Travelling{s, b->hop_host, k.tick}); k.reset_pending[s] = 0; }
+      k.any_reset_pending = false;
     }
     if (sr.any_next) { std::fill(sr.next.begin(), sr.next.end(), 0); sr.any_next = false; }
   }
@@ -476,6 +646,7 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
   const bool sparse = highest >= 0 && highest < Plan::BLK0 && !no_sparse && b->H == 1;
   int occupied = 0;
   for (int s = 0; s < p.n_stages; ++s) occupied += p.hop[s] >= 0 ? 1 : 0;
+  if (!k.resets.empty() && !tick_reset_launch(b, st)) return false;   // (behind the prologue and the tick before, in front of this tick's launch)
   tick_launch(b, sparse, occupied == p.n_stages, st, pairs);
   if (b->r48.on) {  // the step this tick completed: its 48 kHz block is produced by the wrapper launch of the next tick (or of the drain)
     const long long u = step_at(k.plan.count() - 1);
@@ -641,6 +812,7 @@ int tick_enable(BeatriceBatch* b, bool on) {
     }
     if (!hip_ok(hipDeviceSynchronize(), "tick sync")) return -2;
     k.tick = 0; k.n_fed = 0; k.last_feed_tick = -1000; k.snap_cur = -1; k.snap_next = 0;
+    k.resets.clear(); k.reset_pending.assign(b->B, 0); k.any_reset_pending = false; k.reset_launches = 0;
     k.ragged = false;
     for (bool& r : k.step_ragged) r = false;
     for (long long& f : k.fed_step) f = -1;
@@ -651,6 +823,7 @@ int tick_enable(BeatriceBatch* b, bool on) {
   }
   if (!sync_all(b)) return -2;  // drains; streams that have sat steps out come back to the batch's counter (tick_relevel)
   if (k.ragged) return -2;
+  if (k.any_reset_pending && !tick_reset_settle(b)) return -2;   // resets still waiting for their step: the drained form, now
   k.on = false;
   if (b->silent.on && !b->silent.d_rings) b->silent.on = false;   // (the rule was enabled for tick mode only)
   for (int blk = 0; blk < B_NBLOCKS; ++blk) {   // (see above: tick mode's own copies of the K / V tables)

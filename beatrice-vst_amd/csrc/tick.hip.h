@@ -30,6 +30,7 @@
 #include "hip_owned.h"
 #include "rowchain.hip.h"
 #include "tail_stages.hip.h"
+#include "tick_reset.hip.h"
 
 namespace tick {
 
@@ -235,6 +236,21 @@ struct State {
   DevBuf<unsigned long long> d_link_q;      // [H - 1][B][128]: link t = hop t's state for hop t + 1
   DevBuf<unsigned long long> d_link_p;      // [H - 1][B][256]
   PinnedBuf<int> h_link_dead;               // a cell gave a wait up
+  // Streams that start over inside the pipeline (BeatriceBatch_ResetStreamInFlight; tick_reset.hip.h, batch_tick.hip.h tick_reset_*)
+  struct Travelling { int stream, counter; long long tick; };   // a reset on its way: the stream's counter of the step it applies to, the tick that step was fed in
+  std::vector<unsigned char> reset_pending;   // [B] asked for; applies to the next step fed that the stream takes part in
+  bool any_reset_pending = false;
+  std::vector<Travelling> resets;
+  DevBuf<ResetRing> d_reset_rings;            // [n_reset_rings] the pieces of the three arenas that have a window (+ the previous bin)
+  int n_reset_rings = 0;
+  std::vector<int> reset_stage;               // [n_reset_rings] cleared before this stage's tick of the step
+  std::vector<unsigned char> reset_spare;     // [n_reset_rings] ... but for the slot the step itself has written
+  std::vector<int> reset_m;                   // [n_reset_rings] the ring's slot count
+  static constexpr int kResetStaging = 8;
+  StagedRing<int> reset_list;                 // [kResetStaging][reset_list_ints]: a tick's work list, read by the kernels in place
+  size_t reset_list_ints = 0;
+  long long reset_serial = 0, reset_launches = 0;   // lists written so far; ticks that carried a reset launch
+  DevBuf<float> d_gru_keep;                   // [B][256] | [B][128]: the frame a restarted cell's state ring held before the step
 };
 
 }  // namespace tick

@@ -243,6 +243,20 @@ int BeatriceBatch_SetIntonationIntensity(BeatriceBatch* b, int stream, double v)
 int BeatriceBatch_SetPitchCorrection(BeatriceBatch* b, int stream, double v);
 int BeatriceBatch_SetPitchCorrectionType(BeatriceBatch* b, int stream, int type);
 int BeatriceBatch_ResetStream(BeatriceBatch* b, int stream);
+/* The same reset as a per-stream SETTING (stream = -1: every stream): the next step fed that the stream takes part in is the first step
+ * of a new stream.  The effect on that step and all later ones is exactly that of BeatriceBatch_ResetStream followed by that step: all
+ * activation history reads as zeros, the pitch head's previous bin is 0, all four key/value blocks of the target speaker are installed
+ * at that step (BeatriceBatch_FlushSpeaker), every other per-stream setting is kept, the codebook lottery's engine is untouched.  Steps of
+ * the stream already inside the pipeline finish on the old state and land in their slots unchanged.  It is not a mode entry point (no row
+ * in the MODES table) and works in every mode: in plain tick mode (D: H = 1, 2, 4, with or without the silent-block rule) and in host
+ * streaming (E) nothing drains and nothing synchronises -- the call launches nothing, it is host bookkeeping that applies "to the step that
+ * follows" like every other setting, and a stream that sits the next step(s) out is reset at its next present step; in every other mode
+ * (A, B, C, S, F, G, P) it IS BeatriceBatch_ResetStream, with whatever drain that does there.  Range checks and return codes as for
+ * BeatriceBatch_ResetStream.  BeatriceBatch_Synchronize, BeatriceBatch_EnableTickPipeline(b, 0) and BeatriceBatch_StreamFlush may be
+ * called while a reset is still travelling: the drain ticks carry it to the end. */
+int BeatriceBatch_ResetStreamInFlight(BeatriceBatch* b, int stream);
+/* Tick launches since tick mode was entered (fill and drain ticks included); 0 outside tick mode. */
+long long BeatriceBatch_TicksLaunched(const BeatriceBatch* b);
 
 /* One step (H hops, H = 1 unless created with BeatriceBatch_CreateBlock) for every stream.
  * Host variant: in [B][H*160] @16 kHz, out [B][H*240] @24 kHz, synchronous.
