@@ -403,6 +403,8 @@ _BATCH = {
     "BeatriceBatch_BindResidentBlocksRagged": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     "BeatriceBatch_ProcessBlocksRaggedDevice": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "BeatriceBatch_MorphSpeakerStaged": (C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_int, C.c_uint]),
+    "BeatriceBatch_MorphSpeakersInFlight": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _f32p, C.c_int, C.c_uint]),
+    "BeatriceBatch_SpeakerEntryBusy": (C.c_int, [_vp, C.c_int]),
     "BeatriceBatch_GetSpeakerEmbeddings": (C.c_int, [_vp, C.c_int, _f32p, _f32p]),
     "BeatriceBatch_SetTargetSpeaker": (C.c_int, [_vp, C.c_int, C.c_int]),
     "BeatriceBatch_SetTargetSpeakers": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),

@@ -119,6 +119,18 @@ struct BeatriceBatch {
   std::vector<StreamCfg> cfg;
   std::vector<MorphSlot> morph;  // [max_speakers]
   int n_morph_slots = 0;
+  // Which table entries the streams' settings name, kept by COUNT so that no step has to look at every stream (entry_busy;
+  // BeatriceBatch_SpeakerEntryBusy): entry_named[s] is what recount() last counted for stream s -- target, additive and codebook
+  // speaker, the four installed key/value entries (a pending install names the target).  entry_free_at: tick mode, the first tick by
+  // which no step inside the pipeline names the entry any more, stamped when its last reference goes.
+  static constexpr int kNamed = 3 + B_NBLOCKS;
+  std::vector<int> entry_refs;            // [max_speakers]
+  std::vector<long long> entry_free_at;   // [max_speakers]
+  std::vector<int> entry_named;           // [B][kNamed]
+  // BeatriceBatch_MorphSpeakersInFlight: a call's descriptors, read by its kernels in place (the host runs ahead of the device)
+  static constexpr int kMorphStaging = 8;
+  StagedRing<MorphDesc> morph_descs;      // [kMorphStaging][max_speakers]
+  long long morph_calls = 0;
   // the codebook lottery's engine belongs to the stream, as the reference's belongs to the plugin instance
   // (processor_core_2.h:48,145): a stream's draws do not depend on which other streams share its batch
   std::vector<std::mt19937> lottery;  // [B]
@@ -410,8 +422,24 @@ void fill_row_slots(BeatriceBatch* b, int s) {
     for (int hh = 0; hh < b->H; ++hh) b->row_slot[blk][(size_t)s * b->H + hh] = b->cfg[s].kv_slot[blk];
 }
 
+// Brings the entry reference counts up to stream s's settings.  An entry whose last reference goes is still read by the steps inside the
+// tick pipeline that were fed while it was named: the last of them is the step fed last -- or the one about to be fed
+// (next_step_too: advance_kv at several hops per step, whose early hops still run on the blocks installed before).
+void recount(BeatriceBatch* b, int s, bool next_step_too = false) {
+  const StreamCfg& c = b->cfg[s];
+  const int now[BeatriceBatch::kNamed] = {c.target_speaker, c.additive_speaker, c.codebook_speaker, c.kv_slot[0], c.kv_slot[1], c.kv_slot[2], c.kv_slot[3]};
+  int* seen = &b->entry_named[(size_t)s * BeatriceBatch::kNamed];
+  for (int i = 0; i < BeatriceBatch::kNamed; ++i) {
+    if (seen[i] == now[i]) continue;
+    ++b->entry_refs[now[i]];
+    if (--b->entry_refs[seen[i]] == 0) b->entry_free_at[seen[i]] = (next_step_too ? b->tk.tick : b->tk.last_feed_tick) + b->tk.plan.count();
+    seen[i] = now[i];
+  }
+}
+
 void sync_stream_arrays(BeatriceBatch* b, int s) {
   const StreamCfg& c = b->cfg[s];
+  recount(b, s);
   for (int hh = 0; hh < b->H; ++hh) {  // k-NN rows are (stream, hop in step)
     b->host_view<const float*>(b->off.cbT)[(size_t)s * b->H + hh] = b->d_cbT + (size_t)c.codebook_row[hh] * B_PHONE_CH * B_CODEBOOK;
     b->host_view<const float*>(b->off.cnorm)[(size_t)s * b->H + hh] = b->d_cnorm + (size_t)c.codebook_row[hh] * B_CODEBOOK;
@@ -441,6 +469,7 @@ void advance_kv(BeatriceBatch* b) {
         for (int blk = 0; blk < B_NBLOCKS; ++blk) mixed_left = mixed_left || b->row_slot[blk][(size_t)s * H + hh] != c.kv_slot[blk];
       continue;
     }
+    bool installed = false;
     for (int hh = 0; hh < H; ++hh) {  // the hops of this step, each preceded by one block install
       if (c.kv_delay > 0) {
         --c.kv_delay;
@@ -448,12 +477,14 @@ void advance_kv(BeatriceBatch* b) {
         c.kv_slot[c.kv_set_count] = c.target_speaker;
         ++c.kv_set_count;
         advanced = true;
+        installed = true;
       }
       for (int blk = 0; blk < B_NBLOCKS; ++blk) {
         int& rs = b->row_slot[blk][(size_t)s * H + hh];
         if (rs != c.kv_slot[blk]) { rs = c.kv_slot[blk]; dirty[blk] = true; }
       }
     }
+    if (installed) recount(b, s, H > 1);
   }
   int still = 0;
   for (const StreamCfg& c : b->cfg) if (c.kv_set_count < B_NBLOCKS) ++still;
@@ -660,6 +691,13 @@ using modes::Entry;
 modes::Flags flags_of(const BeatriceBatch* b) {
   return {b->tk.on, b->hs.on, b->r48.on, b->rb.on, b->rb.ragged, b->silent.on, b->pipelined, b->io_slots > 0, b->H, b->wrap.ready, b->rw.ready};
 }
+// (a) some stream's settings name the entry; (b) plain tick mode and host streaming: a step that named it is still inside the pipeline
+// (a drain runs the ticks that bring tk.tick up to every stamp)
+bool entry_busy(const BeatriceBatch* b, int e) {
+  if (b->entry_refs[e] > 0) return true;
+  const modes::Mode mode = modes::mode_of(flags_of(b));
+  return (mode == modes::Mode::D || mode == modes::Mode::E) && b->tk.tick < b->entry_free_at[e];
+}
 // The opening of every BeatriceBatch_* entry point: the batch's device for the call's duration, -2 for a missing or unhealthy batch; then
 // -1 for what the batch's mode refuses (batch_modes.h), before anything is drained, synchronised, bound or written.
 #define BATCH_OPEN(b) const DeviceScope dev_((b) ? (b)->device : -1); if (!(b) || !(b)->ok) return -2
@@ -812,6 +850,8 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
        b->d_add_raw.alloc((size_t)S * B_HID, "add") && b->d_frm_raw.alloc((size_t)9 * B_HID, "frm") && b->d_kv_raw.alloc(kvf, "kv");
   b->cfg.assign(B, StreamCfg());
   b->morph.assign(S, MorphSlot());
+  b->entry_refs.assign(S, 0); b->entry_free_at.assign(S, 0); b->entry_named.assign((size_t)B * BeatriceBatch::kNamed, 0);
+  b->entry_refs[0] = B * BeatriceBatch::kNamed;   // (StreamCfg's defaults: every stream on entry 0)
   b->lottery.resize(B);
   for (int s = 0; s < B; ++s) b->lottery[s].seed(5489u + (unsigned)s);
   {  // layout of the settings block (256-byte aligned arrays)
@@ -981,8 +1021,8 @@ int BeatriceBatch_UpdateSpeaker(BeatriceBatch* b, int spk, const float* codebook
 // dropped; processor_core_2.cc:507-532: the eight largest kept, in descending order), then the additive
 // and the 384 key/value embeddings of entry `slot` become weighted spherical means computed on the
 // device (morph.hip), and their projections are refreshed.
-static int morph_into(BeatriceBatch* b, int slot, const float* weights, int n_weights, unsigned seed) {
-  if (!weights || n_weights < 1 || n_weights > 256 || slot < n_weights || slot >= b->max_speakers || n_weights > b->n_speakers) return -1;
+struct MorphPlan { MorphDesc desc; MorphSlot slot; };
+static MorphPlan plan_morph(int slot, const float* weights, int n_weights) {
   std::vector<float> w(weights, weights + n_weights);
   for (float& v : w) if (v < 0.01f) v = 0.0f;
   std::vector<int> order(n_weights);
@@ -990,8 +1030,11 @@ static int morph_into(BeatriceBatch* b, int slot, const float* weights, int n_we
   std::sort(order.begin(), order.end(), [&w](const int x, const int y) -> bool { return w[x] > w[y]; });
   const int keep = std::min(n_weights, 8);
   // SphericalAverage::SetWeights (spherical_average.h:142-199): points in `order` until the first zero weight
-  int n_active = 0, spk[8];
-  float wn[8], sum = 0.0f;
+  MorphPlan p{};
+  int& n_active = p.desc.n_active;
+  int* spk = p.desc.speaker;
+  float* wn = p.desc.weight;
+  float sum = 0.0f;
   for (int i = 0; i < keep; ++i) {
     if (w[order[i]] == 0.0f) break;
     spk[n_active] = order[i]; wn[n_active] = w[order[i]]; ++n_active;
@@ -999,19 +1042,19 @@ static int morph_into(BeatriceBatch* b, int slot, const float* weights, int n_we
   for (int i = 0; i < n_active; ++i) sum += wn[i];
   if (n_active > 0 && sum > 0.0f) { const float inv = 1.0f / sum; for (int i = 0; i < n_active; ++i) wn[i] *= inv; }
   else n_active = 0;
-  bool ok = sync_all(b);
-  ok = ok && spherical_mean_rows(b->d_add_raw, B_HID, 1, B_HID, n_active, spk, wn, b->d_add_raw + (size_t)slot * B_HID, b->stream);
-  ok = ok && spherical_mean_rows(b->d_kv_raw, (size_t)B_KV_LEN * B_KV_CH, B_KV_LEN, B_KV_CH, n_active, spk, wn,
-                                 b->d_kv_raw + (size_t)slot * B_KV_LEN * B_KV_CH, b->stream);
-  if (!ok) return -2;
+  p.desc.slot = slot;
+  p.slot.active = true;
+  p.slot.n_speakers = n_weights;
+  p.slot.n_odds = keep;
+  for (int i = 0; i < 8; ++i) { p.slot.order[i] = i < keep ? order[i] : 0; p.slot.odds[i] = i < keep ? w[order[i]] : 0.0f; }
+  return p;
+}
+// entry p.desc.slot now holds the morph: what the lottery needs, and the engines' one seeding
+static void adopt_morph(BeatriceBatch* b, const MorphPlan& p, unsigned seed) {
+  const int slot = p.desc.slot;
   if (slot >= b->n_speakers) b->n_speakers = slot + 1;
-  if (!project_speakers(b, slot, 1)) return -2;
-  MorphSlot& m = b->morph[slot];
-  if (!m.active) ++b->n_morph_slots;
-  m.active = true;
-  m.n_speakers = n_weights;
-  m.n_odds = keep;
-  for (int i = 0; i < 8; ++i) { m.order[i] = i < keep ? order[i] : 0; m.odds[i] = i < keep ? w[order[i]] : 0.0f; }
+  if (!b->morph[slot].active) ++b->n_morph_slots;
+  b->morph[slot] = p.slot;
   // The engines are seeded ONCE per batch, as the reference seeds its engine once per instance (processor_core_2.h:48,145) and
   // never again when morph weights move (:94-121): only the first morph of the batch's life applies `seed`; a caller that
   // moves weights every step keeps each stream's draw SEQUENCE running, and a morph on one entry leaves the draws of the
@@ -1020,6 +1063,22 @@ static int morph_into(BeatriceBatch* b, int slot, const float* weights, int n_we
     for (int st = 0; st < b->B; ++st) b->lottery[st].seed(seed + (unsigned)st);
     b->lottery_seeded = true;
   }
+}
+static bool morph_weights_ok(const BeatriceBatch* b, const float* weights, int n_weights) {
+  return weights && n_weights >= 1 && n_weights <= 256 && n_weights <= b->n_speakers;
+}
+static int morph_into(BeatriceBatch* b, int slot, const float* weights, int n_weights, unsigned seed) {
+  if (!morph_weights_ok(b, weights, n_weights) || slot < n_weights || slot >= b->max_speakers) return -1;
+  const MorphPlan p = plan_morph(slot, weights, n_weights);
+  const MorphDesc& d = p.desc;
+  bool ok = sync_all(b);
+  ok = ok && spherical_mean_rows(b->d_add_raw, B_HID, 1, B_HID, d.n_active, d.speaker, d.weight, b->d_add_raw + (size_t)slot * B_HID, b->stream);
+  ok = ok && spherical_mean_rows(b->d_kv_raw, (size_t)B_KV_LEN * B_KV_CH, B_KV_LEN, B_KV_CH, d.n_active, d.speaker, d.weight,
+                                 b->d_kv_raw + (size_t)slot * B_KV_LEN * B_KV_CH, b->stream);
+  if (!ok) return -2;
+  if (slot >= b->n_speakers) b->n_speakers = slot + 1;
+  if (!project_speakers(b, slot, 1)) return -2;
+  adopt_morph(b, p, seed);
   return 0;
 }
 int BeatriceBatch_MorphSpeaker(BeatriceBatch* b, int slot, const float* weights, int n_weights, unsigned seed) {
@@ -1063,6 +1122,71 @@ int BeatriceBatch_MorphSpeakerStaged(BeatriceBatch* b, int slot, int from_slot, 
   b->pending_kv = 0;
   for (const StreamCfg& c : b->cfg) if (c.kv_set_count < B_NBLOCKS) ++b->pending_kv;
   return 0;
+}
+// Many entries in one call, and in plain tick mode and host streaming WITHOUT the drain (beatrice_batch.h): the entries are refused
+// while anything still reads them (entry_busy), so their tables may be rewritten between two ticks -- two launches on the batch's stream
+// in front of the next tick (morph.hip: all solves, all projections), the descriptors in a pinned ring because the host runs ahead.
+int BeatriceBatch_MorphSpeakersInFlight(BeatriceBatch* b, int n, const int* slots, const int* from_slots, const float* weights, int n_weights,
+                                        unsigned seed) {
+  BATCH_OPEN(b);
+  const int S = b->max_speakers;
+  if (n < 1 || n > S || !slots || !from_slots || !morph_weights_ok(b, weights, n_weights)) return -1;
+  std::vector<char> is_slot(S, 0), is_from(S, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < n_weights || slots[i] >= S || is_slot[slots[i]]) return -1;
+    is_slot[slots[i]] = 1;
+  }
+  for (int i = 0; i < n; ++i) {
+    const int f = from_slots[i];
+    if (f == -1) continue;
+    if (f < 0 || f >= S || is_slot[f] || is_from[f]) return -1;   // (is_slot: its own slot, or another pair's)
+    is_from[f] = 1;
+  }
+  for (int i = 0; i < n; ++i) if (entry_busy(b, slots[i])) return -3;
+  const modes::Mode mode = modes::mode_of(flags_of(b));
+  const bool in_flight = mode == modes::Mode::D || mode == modes::Mode::E;
+  if (!b->morph_descs.entries() && !b->morph_descs.alloc(BeatriceBatch::kMorphStaging, (size_t)S, "morph descriptors")) return -2;
+  if (!in_flight && !sync_all(b)) return -2;
+  const int ring = (int)(b->morph_calls % BeatriceBatch::kMorphStaging);
+  MorphDesc* descs = b->morph_descs.claim(ring);
+  if (!descs) return -2;
+  std::vector<MorphPlan> plans(n);
+  for (int i = 0; i < n; ++i) {
+    plans[i] = plan_morph(slots[i], weights + (size_t)i * n_weights, n_weights);
+    descs[i] = plans[i].desc;
+  }
+  const EmbedWeights& w = b->embed_m->w;
+  MorphProjectArgs pa{};
+  pa.descs = descs; pa.n = n; pa.n_entries = S;
+  pa.add_raw = b->d_add_raw; pa.kv_raw = b->d_kv_raw; pa.add_w = w.add_w; pa.add_b = w.add_b; pa.add_tab = b->wave.d_add_tab;
+  for (int blk = 0; blk < B_NBLOCKS; ++blk) {
+    pa.k_w[blk] = w.k_w[blk]; pa.k_b[blk] = w.k_b[blk]; pa.v_w[blk] = w.v_w[blk]; pa.v_b[blk] = w.v_b[blk];
+    pa.kt[blk] = b->wave.d_kt[blk]; pa.v[blk] = b->wave.d_v[blk]; pa.kt_plain[blk] = b->wave.d_ktp[blk]; pa.v_plain[blk] = b->wave.d_vp[blk];
+  }
+  bool ok = spherical_mean_entries(descs, n, S, b->d_add_raw, b->d_kv_raw, b->stream) && morph_project_entries(pa, b->stream);
+  ok = b->morph_descs.mark(ring, b->stream) && ok;
+  b->morph_calls += 1;
+  if (!in_flight) ok = hip_ok(hipStreamSynchronize(b->stream), "morph entries") && ok;
+  if (!ok) return -2;
+  for (const MorphPlan& p : plans) adopt_morph(b, p, seed);
+  for (int s = 0; s < b->B; ++s) {   // the streams on a from_slot move over, on BeatriceBatch_MorphSpeakerStaged's timeline
+    StreamCfg& c = b->cfg[s];
+    if (!is_from[c.target_speaker]) continue;
+    int to = -1;
+    for (int i = 0; i < n && to < 0; ++i) if (from_slots[i] == c.target_speaker) to = slots[i];
+    c.target_speaker = to;
+    c.additive_speaker = to;
+    c.kv_set_count = 0;
+    c.kv_delay = 4;
+    sync_stream_arrays(b, s);
+  }
+  b->pending_kv = 0;
+  for (const StreamCfg& c : b->cfg) if (c.kv_set_count < B_NBLOCKS) ++b->pending_kv;
+  return 0;
+}
+int BeatriceBatch_SpeakerEntryBusy(const BeatriceBatch* b, int entry) {
+  if (!b || !b->ok || entry < 0 || entry >= b->max_speakers) return -1;
+  return entry_busy(b, entry) ? 1 : 0;
 }
 // the codebook lottery's engine of one stream (or of all, -1): std::mt19937(seed), e.g. a value derived from the
 // stream's global identity when streams are sharded over several batches / GPUs

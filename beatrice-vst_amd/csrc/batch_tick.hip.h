@@ -812,6 +812,7 @@ int tick_enable(BeatriceBatch* b, bool on) {
     }
     if (!hip_ok(hipDeviceSynchronize(), "tick sync")) return -2;
     k.tick = 0; k.n_fed = 0; k.last_feed_tick = -1000; k.snap_cur = -1; k.snap_next = 0;
+    std::fill(b->entry_free_at.begin(), b->entry_free_at.end(), 0);   // (stamps of an earlier stay in tick mode: the pipeline is empty)
     k.resets.clear(); k.reset_pending.assign(b->B, 0); k.any_reset_pending = false; k.reset_launches = 0;
     k.ragged = false;
     for (bool& r : k.step_ragged) r = false;

@@ -299,5 +299,19 @@ void codebook_prepare(const float* d_cb, int n, float* d_cbT, float* d_cnorm, hi
 // n < n_active <= 8, weights normalised and descending; dim = 128 or 256; one wavefront per row
 bool spherical_mean_rows(const float* d_table, size_t speaker_stride, int rows, int dim, int n_active, const int* speakers,
                          const float* weights, float* d_out, hipStream_t stream);
+// The same for n table entries in two launches (BeatriceBatch_MorphSpeakersInFlight).  One descriptor per entry, read by the kernels
+// from memory -- pinned host memory the caller writes ahead of the device: entry `slot` of the raw tables becomes the mean of entries
+// speaker[0 .. n_active) (results bit-identical to spherical_mean_rows), then its additive row and the key/value tables of all four
+// blocks are projected (bit-identical to embed_project_rows / embed_project_kv).  n_entries bounds every index a descriptor names.
+struct MorphDesc { int slot, n_active; int speaker[8]; float weight[8]; };
+bool spherical_mean_entries(const MorphDesc* descs, int n, int n_entries, float* d_add_raw, float* d_kv_raw, hipStream_t stream);
+struct MorphProjectArgs {
+  const MorphDesc* descs; int n, n_entries;
+  const float *add_raw, *kv_raw, *add_w, *add_b;
+  const float *k_w[B_NBLOCKS], *k_b[B_NBLOCKS], *v_w[B_NBLOCKS], *v_b[B_NBLOCKS];
+  float* add_tab;
+  float *kt[B_NBLOCKS], *v[B_NBLOCKS], *kt_plain[B_NBLOCKS], *v_plain[B_NBLOCKS];   // (plain: nullptr when the batch holds no such copies)
+};
+bool morph_project_entries(const MorphProjectArgs& a, hipStream_t stream);
 
 }  // namespace bhip

@@ -225,6 +225,30 @@ int BeatriceBatch_SeedLottery(BeatriceBatch* b, int stream, unsigned seed);
  * eight hops; as in the reference, new blocks are then never installed while the weights keep moving: each call restarts the
  * four-hop wait). */
 int BeatriceBatch_MorphSpeakerStaged(BeatriceBatch* b, int slot, int from_slot, const float* weights, int n_weights, unsigned seed);
+/* The same for n table entries in ONE call, and without the drain where the pipeline allows it.  For every i < n:
+ *   from_slots[i] >= 0:  exactly BeatriceBatch_MorphSpeakerStaged(b, slots[i], from_slots[i], weights + i * n_weights, n_weights, seed);
+ *   from_slots[i] == -1: exactly BeatriceBatch_MorphSpeaker on an entry no stream is on -- the entry is computed, no stream moves.
+ * Same weight preparation, same lottery rule (seeded once per batch life, seed + stream), same timeline for the streams that move
+ * (additive embedding and odds on the next hop, a four-hop wait, then one key/value block per hop).  All n * 385 spherical means run in
+ * one launch and all projections in a second one (results bit-identical to the single-entry calls; a morph entry's codebook is not
+ * touched).  In plain tick mode (D: H = 1, 2, 4, with or without the silent-block rule) and in host streaming (E) nothing drains and
+ * nothing synchronises: the two launches go onto the batch's stream in front of the next tick and the call returns; in every other mode
+ * it drains as the single-entry calls do.  It is a setting, not a mode entry point (no row in the MODES table).
+ * All or nothing.  -1 and no change (no launch, no drain, no seeding): n < 1 or n > max_speakers; the n_weights rules of
+ * BeatriceBatch_MorphSpeaker; a slot outside [n_weights, max_speakers); a slot twice; a from_slot twice; a from_slot out of range,
+ * equal to its own slot or to another pair's slot.  -3 and no change: some slot is busy (BeatriceBatch_SpeakerEntryBusy).
+ * What rotation costs: an entry stays busy until the streams that left it have installed their new key/value blocks (eight hops
+ * after the call that moved them, later if the weights move again first) AND, in D and E, until the last step that named it has left
+ * the pipeline, BeatriceBatch_TickStages() ticks on.  A stream whose weights move every step therefore needs about TickStages() + 2
+ * entries to rotate over, at about 3.1 MB of projected tables per entry (four blocks, K and V, in two layouts).  Rewriting an entry
+ * that streams are on, and BeatriceBatch_UpdateSpeaker without a drain, are not offered. */
+int BeatriceBatch_MorphSpeakersInFlight(BeatriceBatch* b, int n, const int* slots, const int* from_slots,
+                                        const float* weights /* [n][n_weights] */, int n_weights, unsigned seed);
+/* 1: table entry `entry` is busy, 0: free to be a slot of BeatriceBatch_MorphSpeakersInFlight, -1: bad argument.  Busy means (a) some
+ * stream's current settings name it -- as target, additive or codebook speaker, or as an installed or pending key/value entry -- or
+ * (b) in D and E, a step that named it was fed fewer than BeatriceBatch_TickStages() ticks ago and the pipeline has not been drained
+ * since: that step's later stages still read the entry's additive row and key/value tables.  Host bookkeeping; launches nothing. */
+int BeatriceBatch_SpeakerEntryBusy(const BeatriceBatch* b, int entry);
 /* Raw embeddings of a table entry as currently held on the device: additive [256], key_value [384][128]. */
 int BeatriceBatch_GetSpeakerEmbeddings(BeatriceBatch* b, int speaker, float* additive, float* key_value);
 
