@@ -405,6 +405,8 @@ _BATCH = {
     "BeatriceBatch_MorphSpeakerStaged": (C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_int, C.c_uint]),
     "BeatriceBatch_MorphSpeakersInFlight": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _f32p, C.c_int, C.c_uint]),
     "BeatriceBatch_SpeakerEntryBusy": (C.c_int, [_vp, C.c_int]),
+    "BeatriceBatch_InstallSpeakersInFlight": (C.c_int, [_vp, C.c_int, _i32p, _f32p, _f32p, _f32p]),
+    "BeatriceBatch_MaxInstallEntries": (C.c_int, [_vp]),
     "BeatriceBatch_GetSpeakerEmbeddings": (C.c_int, [_vp, C.c_int, _f32p, _f32p]),
     "BeatriceBatch_SetTargetSpeaker": (C.c_int, [_vp, C.c_int, C.c_int]),
     "BeatriceBatch_SetTargetSpeakers": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),

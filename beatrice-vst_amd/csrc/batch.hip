@@ -131,6 +131,12 @@ struct BeatriceBatch {
   static constexpr int kMorphStaging = 8;
   StagedRing<MorphDesc> morph_descs;      // [kMorphStaging][max_speakers]
   long long morph_calls = 0;
+  // BeatriceBatch_InstallSpeakersInFlight: a call's tables and its descriptors (only `slot` is used), likewise; allocated by the first
+  // call -- kInstallStaging x min(kInstallEntries, max_speakers) x 449 KB of pinned memory, 29 MB at most
+  static constexpr int kInstallStaging = 4, kInstallEntries = 16;
+  StagedRing<float> install_tables;       // [kInstallStaging][cap][kInstallEntryFloats]
+  PinnedBuf<MorphDesc> install_descs;     // [kInstallStaging][cap], an entry's readers are those of install_tables' entry
+  long long install_calls = 0;
   // the codebook lottery's engine belongs to the stream, as the reference's belongs to the plugin instance
   // (processor_core_2.h:48,145): a stream's draws do not depend on which other streams share its batch
   std::vector<std::mt19937> lottery;  // [B]
@@ -693,10 +699,28 @@ modes::Flags flags_of(const BeatriceBatch* b) {
 }
 // (a) some stream's settings name the entry; (b) plain tick mode and host streaming: a step that named it is still inside the pipeline
 // (a drain runs the ticks that bring tk.tick up to every stamp)
-bool entry_busy(const BeatriceBatch* b, int e) {
+bool entry_named(const BeatriceBatch* b, int e) {
   if (b->entry_refs[e] > 0) return true;
   const modes::Mode mode = modes::mode_of(flags_of(b));
   return (mode == modes::Mode::D || mode == modes::Mode::E) && b->tk.tick < b->entry_free_at[e];
+}
+// ... or (c) its CODEBOOK may be what a step drew: recount() counts the codebook of a stream's last hop, not the lottery's candidates
+// (draw_codebooks), so an entry is also busy while an active morph entry m that is itself named -- (a) or (b): the steps that could have
+// drawn from m's list are exactly the steps that named m -- lists it with positive odds, or with any odds when all of m's are zero (the
+// lottery then draws from all of m's speakers).  A walk over the table's morph entries at call time; no step looks at this.
+bool entry_busy(const BeatriceBatch* b, int e) {
+  if (entry_named(b, e)) return true;
+  if (b->n_morph_slots == 0) return false;
+  for (int m = 0; m < b->max_speakers; ++m) {
+    const MorphSlot& ms = b->morph[m];
+    if (!ms.active || m == e) continue;
+    float sum = 0.0f;
+    for (int i = 0; i < ms.n_odds; ++i) sum += ms.odds[i];
+    bool listed = sum <= std::numeric_limits<float>::epsilon() && e < ms.n_speakers;
+    for (int i = 0; i < ms.n_odds; ++i) listed = listed || (ms.order[i] == e && ms.odds[i] > 0.0f);
+    if (listed && entry_named(b, m)) return true;
+  }
+  return false;
 }
 // The opening of every BeatriceBatch_* entry point: the batch's device for the call's duration, -2 for a missing or unhealthy batch; then
 // -1 for what the batch's mode refuses (batch_modes.h), before anything is drained, synchronised, bound or written.
@@ -1187,6 +1211,67 @@ int BeatriceBatch_MorphSpeakersInFlight(BeatriceBatch* b, int n, const int* slot
 int BeatriceBatch_SpeakerEntryBusy(const BeatriceBatch* b, int entry) {
   if (!b || !b->ok || entry < 0 || entry >= b->max_speakers) return -1;
   return entry_busy(b, entry) ? 1 : 0;
+}
+// BeatriceBatch_UpdateSpeaker for n entries in one call, and in plain tick mode and host streaming without the drain, on the same terms
+// as the morph call above: entries nothing reads (entry_busy) are rewritten between two ticks by two launches on the batch's stream.  The
+// caller's tables are copied into a pinned ring entry here, on the calling thread; install_entries_kernel (install.hip) reads them in
+// place and writes the raw tables, the transposed codebooks and their norms, morph_project_kernel (morph.hip) projects the rest.
+int BeatriceBatch_MaxInstallEntries(const BeatriceBatch* b) { return b ? std::min(BeatriceBatch::kInstallEntries, b->max_speakers) : 0; }
+int BeatriceBatch_InstallSpeakersInFlight(BeatriceBatch* b, int n, const int* entries, const float* codebooks, const float* additive,
+                                          const float* key_value) {
+  BATCH_OPEN(b);
+  const int S = b->max_speakers, cap = BeatriceBatch_MaxInstallEntries(b);
+  if (n < 1 || n > cap || !entries || !codebooks || !additive || !key_value) return -1;
+  std::vector<char> is_entry(S, 0);
+  for (int i = 0; i < n; ++i) {
+    if (entries[i] < 0 || entries[i] >= S || is_entry[entries[i]]) return -1;
+    is_entry[entries[i]] = 1;
+  }
+  for (int i = 0; i < n; ++i) if (entry_busy(b, entries[i])) return -3;
+  const modes::Mode mode = modes::mode_of(flags_of(b));
+  const bool in_flight = mode == modes::Mode::D || mode == modes::Mode::E;
+  if (!b->install_tables.entries()) {
+    StagedRing<float> tables;
+    PinnedBuf<MorphDesc> descs;
+    if (!tables.alloc(BeatriceBatch::kInstallStaging, (size_t)cap * kInstallEntryFloats, "install staging") ||
+        !descs.alloc((size_t)BeatriceBatch::kInstallStaging * cap, "install descriptors")) return -2;
+    b->install_tables = std::move(tables); b->install_descs = std::move(descs);
+  }
+  if (!in_flight && !sync_all(b)) return -2;
+  // (the ring entry of kInstallStaging calls ago: a wait only if the device is that many installs behind the host)
+  const int ring = (int)(b->install_calls % BeatriceBatch::kInstallStaging);
+  float* staged = b->install_tables.claim(ring);
+  if (!staged) return -2;
+  MorphDesc* descs = b->install_descs + (size_t)ring * cap;
+  constexpr size_t n_cb = (size_t)B_CODEBOOK * B_PHONE_CH, n_kv = (size_t)B_KV_LEN * B_KV_CH;
+  for (int i = 0; i < n; ++i) {
+    float* dst = staged + (size_t)i * kInstallEntryFloats;
+    std::memcpy(dst, codebooks + (size_t)i * n_cb, sizeof(float) * n_cb);
+    std::memcpy(dst + n_cb, additive + (size_t)i * B_HID, sizeof(float) * B_HID);
+    std::memcpy(dst + n_cb + B_HID, key_value + (size_t)i * n_kv, sizeof(float) * n_kv);
+    descs[i] = MorphDesc{};
+    descs[i].slot = entries[i];
+  }
+  const EmbedWeights& w = b->embed_m->w;
+  MorphProjectArgs pa{};
+  pa.descs = descs; pa.n = n; pa.n_entries = S;
+  pa.add_raw = b->d_add_raw; pa.kv_raw = b->d_kv_raw; pa.add_w = w.add_w; pa.add_b = w.add_b; pa.add_tab = b->wave.d_add_tab;
+  for (int blk = 0; blk < B_NBLOCKS; ++blk) {
+    pa.k_w[blk] = w.k_w[blk]; pa.k_b[blk] = w.k_b[blk]; pa.v_w[blk] = w.v_w[blk]; pa.v_b[blk] = w.v_b[blk];
+    pa.kt[blk] = b->wave.d_kt[blk]; pa.v[blk] = b->wave.d_v[blk]; pa.kt_plain[blk] = b->wave.d_ktp[blk]; pa.v_plain[blk] = b->wave.d_vp[blk];
+  }
+  bool ok = install_entries(descs, staged, n, S, b->d_cb_raw, b->d_add_raw, b->d_kv_raw, b->d_cbT, b->d_cnorm, b->stream) &&
+            morph_project_entries(pa, b->stream);
+  ok = b->install_tables.mark(ring, b->stream) && ok;
+  b->install_calls += 1;
+  if (!in_flight) ok = hip_ok(hipStreamSynchronize(b->stream), "install entries") && ok;
+  if (!ok) return -2;
+  for (int i = 0; i < n; ++i) {
+    const int e = entries[i];
+    if (e >= b->n_speakers) b->n_speakers = e + 1;
+    if (b->morph[e].active) { b->morph[e].active = false; --b->n_morph_slots; }   // the caller's data replaces a morph
+  }
+  return 0;
 }
 // the codebook lottery's engine of one stream (or of all, -1): std::mt19937(seed), e.g. a value derived from the
 // stream's global identity when streams are sharded over several batches / GPUs

@@ -313,5 +313,13 @@ struct MorphProjectArgs {
   float *kt[B_NBLOCKS], *v[B_NBLOCKS], *kt_plain[B_NBLOCKS], *v_plain[B_NBLOCKS];   // (plain: nullptr when the batch holds no such copies)
 };
 bool morph_project_entries(const MorphProjectArgs& a, hipStream_t stream);
+// A caller's tables into n table entries in one launch (BeatriceBatch_InstallSpeakersInFlight; install.hip).  staged[i], pinned host
+// memory the caller wrote ahead of the device, holds entry descs[i].slot's codebook [512][128], additive row [256] and key/value tokens
+// [384][128] back to back (kInstallEntryFloats); only `slot` of a descriptor is read, and one outside [0, n_entries) is skipped.  Writes
+// the three raw tables at the entries' places and each entry's transposed codebook and squared norms (the bits of codebook_prepare);
+// morph_project_entries over the same descriptors then projects the rest.
+constexpr size_t kInstallEntryFloats = (size_t)B_CODEBOOK * B_PHONE_CH + B_HID + (size_t)B_KV_LEN * B_KV_CH;
+bool install_entries(const MorphDesc* descs, const float* staged, int n, int n_entries, float* d_cb_raw, float* d_add_raw, float* d_kv_raw,
+                     float* d_cbT, float* d_cnorm, hipStream_t stream);
 
 }  // namespace bhip

@@ -241,14 +241,40 @@ int BeatriceBatch_MorphSpeakerStaged(BeatriceBatch* b, int slot, int from_slot, 
  * after the call that moved them, later if the weights move again first) AND, in D and E, until the last step that named it has left
  * the pipeline, BeatriceBatch_TickStages() ticks on.  A stream whose weights move every step therefore needs about TickStages() + 2
  * entries to rotate over, at about 3.1 MB of projected tables per entry (four blocks, K and V, in two layouts).  Rewriting an entry
- * that streams are on, and BeatriceBatch_UpdateSpeaker without a drain, are not offered. */
+ * that streams are on is not offered; a caller's own tables go into free entries without a drain through
+ * BeatriceBatch_InstallSpeakersInFlight. */
 int BeatriceBatch_MorphSpeakersInFlight(BeatriceBatch* b, int n, const int* slots, const int* from_slots,
                                         const float* weights /* [n][n_weights] */, int n_weights, unsigned seed);
-/* 1: table entry `entry` is busy, 0: free to be a slot of BeatriceBatch_MorphSpeakersInFlight, -1: bad argument.  Busy means (a) some
+/* 1: table entry `entry` is busy, 0: free to be a slot of BeatriceBatch_MorphSpeakersInFlight or an entry of
+ * BeatriceBatch_InstallSpeakersInFlight, -1: bad argument.  Busy means (a) some
  * stream's current settings name it -- as target, additive or codebook speaker, or as an installed or pending key/value entry -- or
  * (b) in D and E, a step that named it was fed fewer than BeatriceBatch_TickStages() ticks ago and the pipeline has not been drained
- * since: that step's later stages still read the entry's additive row and key/value tables.  Host bookkeeping; launches nothing. */
+ * since: that step's later stages still read the entry's additive row and key/value tables -- or (c) an active morph entry that is
+ * itself busy by (a) or (b) lists it with positive odds (with any odds when all of the morph's weights were dropped: the lottery then
+ * draws from all of its speakers): a step of a stream on that morph may have drawn the entry's codebook.  Host bookkeeping; launches
+ * nothing. */
 int BeatriceBatch_SpeakerEntryBusy(const BeatriceBatch* b, int entry);
+/* New voices into a running batch: for every i < n the effect on every later step is exactly that of
+ * BeatriceBatch_UpdateSpeaker(b, entries[i], codebooks + i * 512 * 128, additive + i * 256, key_value + i * 384 * 128) with all three
+ * tables given -- the raw tables, the transposed codebook with its norms, the additive projection and the key/value projections of all
+ * four blocks hold the same bits, the table grows to cover the entry, an active morph on the entry ends.  No stream moves: point streams
+ * at the new entries afterwards with BeatriceBatch_SetTargetSpeaker(s).  All three tables are required (NULL: -1), unlike
+ * BeatriceBatch_UpdateSpeaker's optional ones.
+ * Two launches per call whatever n is (all tables from staging, all projections).  In plain tick mode (D: H = 1, 2, 4, with or without
+ * the silent-block rule) and in host streaming (E) nothing drains and nothing synchronises: the launches go onto the batch's stream in
+ * front of the next tick and the call returns; in every other mode it drains first and waits for its launches, as the single-entry call
+ * does.  It is a setting, not a mode entry point (no row in the MODES table).
+ * The caller's arrays may be reused as soon as the call returns: the call copies them into pinned staging on the calling thread, about
+ * 449 KB per entry (tens of microseconds each).  The staging is a ring of 4 calls x BeatriceBatch_MaxInstallEntries() entries, allocated
+ * by the first call (29 MB of pinned memory at the cap of 16); a fifth call waits only if the device has not yet run the first one's
+ * launches.
+ * All or nothing.  -1 and no change (no launch, no drain, nothing staged): n < 1 or n > BeatriceBatch_MaxInstallEntries(b); a NULL
+ * pointer; an entry outside [0, max_speakers); an entry twice.  -3 and no change: some entry is busy (BeatriceBatch_SpeakerEntryBusy).
+ * -2: HIP or allocation failure. */
+int BeatriceBatch_InstallSpeakersInFlight(BeatriceBatch* b, int n, const int* entries, const float* codebooks /* [n][512][128] */,
+                                          const float* additive /* [n][256] */, const float* key_value /* [n][384][128] */);
+/* The most entries one BeatriceBatch_InstallSpeakersInFlight call takes: min(16, max_speakers). */
+int BeatriceBatch_MaxInstallEntries(const BeatriceBatch* b);
 /* Raw embeddings of a table entry as currently held on the device: additive [256], key_value [384][128]. */
 int BeatriceBatch_GetSpeakerEmbeddings(BeatriceBatch* b, int speaker, float* additive, float* key_value);
 
