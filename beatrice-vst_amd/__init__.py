@@ -367,6 +367,7 @@ _BATCH = {
     "BeatriceHip_GetDevice": (C.c_int, []),
     "BeatriceBatch_Device": (C.c_int, [_vp]),
     "BeatriceHip_MathSelfTest": (C.c_longlong, [C.c_int, C.POINTER(C.c_uint)]),
+    "BeatriceHip_MathEval": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
     "BeatriceHip_InvalidateCodebook": (None, [_vp, _vp]),
     "BeatriceHip_InjectTeamTimeout": (C.c_int, [_vp]),
     "BeatriceHip_InjectTeamTimeoutPhone": (C.c_int, [_vp]),

@@ -3,6 +3,9 @@
 // the functions under test are device code: BeatriceHip_MathSelfTest(which) sweeps all 2^32 float32 bit patterns (NaNs
 // excluded) and returns the number of inputs whose results differ in any bit; -1 on a HIP failure.
 //   which: 0 exp2 vs exp, 1 tanh2 vs tanh, 2 gelu2 vs gelu, 3 sigmoid2 vs sigmoid
+// BeatriceHip_MathEval(which, bits, n, out_bits) evaluates one function at n caller-chosen points and hands the result bits back, so a
+// test can compare the device functions with oracle/spec_math.h directly (tests/test_gpu_spec_math.py).
+//   which: 0 exp, 1 tanh, 2 gelu, 3 sigmoid, 4 log, 5 lrelu (scalar); 6 exp2, 7 tanh2, 8 gelu2, 9 sigmoid2 (points taken in pairs)
 #include <hip/hip_runtime.h>
 
 #include "engine.h"
@@ -30,7 +33,69 @@ __global__ __launch_bounds__(256) void sweep_kernel(unsigned long long* bad, uns
   }
   if (mine) atomicAdd(bad, mine);
 }
+
+template <int WHICH>
+__global__ __launch_bounds__(256) void eval_kernel(const uint32_t* __restrict__ bits, size_t n, uint32_t* __restrict__ out) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  if (WHICH < 6) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      const float x = __uint_as_float(bits[i]);
+      float y;
+      if (WHICH == 0) y = bsp::exp(x);
+      else if (WHICH == 1) y = bsp::tanh(x);
+      else if (WHICH == 2) y = bsp::gelu(x);
+      else if (WHICH == 3) y = bsp::sigmoid(x);
+      else if (WHICH == 4) y = bsp::log(x);
+      else y = bsp::lrelu(x);
+      out[i] = __float_as_uint(y);
+    }
+  } else {
+    // pair p holds points 2p and 2p + 1; an odd count pairs the last point with itself
+    const size_t pairs = (n + 1) / 2;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < pairs; p += stride) {
+      const size_t i0 = 2 * p, i1 = (2 * p + 1 < n) ? 2 * p + 1 : i0;
+      const bsp::f32x2 x{__uint_as_float(bits[i0]), __uint_as_float(bits[i1])};
+      bsp::f32x2 y;
+      if (WHICH == 6) y = bsp::exp2(x);
+      else if (WHICH == 7) y = bsp::tanh2(x);
+      else if (WHICH == 8) y = bsp::gelu2(x);
+      else y = bsp::sigmoid2(x);
+      out[i0] = __float_as_uint(y.x);
+      if (i1 != i0) out[i1] = __float_as_uint(y.y);
+    }
+  }
+}
 }  // namespace
+
+extern "C" int BeatriceHip_MathEval(int which, const uint32_t* bits, size_t n, uint32_t* out_bits) {
+  if (which < 0 || which > 9 || (n && (!bits || !out_bits))) return -1;
+  if (n == 0) return 0;
+  uint32_t *d_in = nullptr, *d_out = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&d_in), n * 4) != hipSuccess) return -1;
+  if (hipMalloc(reinterpret_cast<void**>(&d_out), n * 4) != hipSuccess) { (void)hipFree(d_in); return -1; }
+  bool ok = hipMemcpy(d_in, bits, n * 4, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    const size_t blocks = (n + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096)), block(256);
+    switch (which) {
+      case 0: hipLaunchKernelGGL(eval_kernel<0>, grid, block, 0, 0, d_in, n, d_out); break;
+      case 1: hipLaunchKernelGGL(eval_kernel<1>, grid, block, 0, 0, d_in, n, d_out); break;
+      case 2: hipLaunchKernelGGL(eval_kernel<2>, grid, block, 0, 0, d_in, n, d_out); break;
+      case 3: hipLaunchKernelGGL(eval_kernel<3>, grid, block, 0, 0, d_in, n, d_out); break;
+      case 4: hipLaunchKernelGGL(eval_kernel<4>, grid, block, 0, 0, d_in, n, d_out); break;
+      case 5: hipLaunchKernelGGL(eval_kernel<5>, grid, block, 0, 0, d_in, n, d_out); break;
+      case 6: hipLaunchKernelGGL(eval_kernel<6>, grid, block, 0, 0, d_in, n, d_out); break;
+      case 7: hipLaunchKernelGGL(eval_kernel<7>, grid, block, 0, 0, d_in, n, d_out); break;
+      case 8: hipLaunchKernelGGL(eval_kernel<8>, grid, block, 0, 0, d_in, n, d_out); break;
+      default: hipLaunchKernelGGL(eval_kernel<9>, grid, block, 0, 0, d_in, n, d_out); break;
+    }
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+         hipMemcpy(out_bits, d_out, n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  (void)hipFree(d_in);
+  (void)hipFree(d_out);
+  return ok ? 0 : -1;
+}
 
 extern "C" long long BeatriceHip_MathSelfTest(int which, unsigned* first_bad_bits) {
   unsigned long long* d_bad = nullptr;

@@ -28,6 +28,7 @@
 #define BEATRICE_BATCH_H_
 
 #include <stddef.h>
+#include <stdint.h>
 
 #include "beatrice_abi.h"
 
@@ -81,6 +82,12 @@ int BeatriceBatch_Device(const BeatriceBatch* b);
  * which: 0 exp, 1 tanh, 2 gelu, 3 sigmoid.  Returns the number of inputs whose results differ in any bit (0 = identical),
  * *first_bad_bits = the lowest such input (0xffffffff when none); -1 on a HIP failure or an unknown `which`. */
 long long BeatriceHip_MathSelfTest(int which, unsigned* first_bad_bits);
+
+/* Test support: one of MODEL_SPEC 2.1's functions, as the device computes it, at n caller-chosen points.  `bits` and `out_bits` are
+ * host arrays of n float32 bit patterns.  which: 0 exp, 1 tanh, 2 gelu, 3 sigmoid, 4 log (positive normal arguments), 5 lrelu -- the
+ * scalar device functions; 6 exp, 7 tanh, 8 gelu, 9 sigmoid in their packed forms, the points taken in pairs (2p, 2p + 1; an odd
+ * count pairs the last point with itself).  Returns 0; -1 on a HIP failure, an unknown `which` or a null array with n > 0. */
+int BeatriceHip_MathEval(int which, const uint32_t* bits, size_t n, uint32_t* out_bits);
 
 /* Device-resident parameter blobs, for loading a model on several GPUs from ONE file read.
  * kind: 1 phone extractor, 2 pitch estimator, 3 waveform generator, 4 embedding setter; `model` the matching object.

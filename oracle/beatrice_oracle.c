@@ -1021,3 +1021,23 @@ static Beatrice_ErrorCode lrows_open(const char* path, float** blob, int* rows) 
 
 LEGACY_GENERATION(Beatrice20a2)
 LEGACY_GENERATION(Beatrice20b1)
+
+/* ---- test support: oracle/spec_math.h at caller-chosen points (the counterpart of the product's BeatriceHip_MathEval) ----
+ * which: 0 exp, 1 tanh, 2 gelu, 3 sigmoid, 4 log, 5 lrelu; in and out are float32 bit patterns.  Returns 0, -1 on an unknown `which`. */
+int BeatriceOracle_MathEval(int which, const uint32_t* bits, size_t n, uint32_t* out_bits) {
+  if (which < 0 || which > 5) return -1;
+  for (size_t i = 0; i < n; ++i) {
+    const float x = sp_from_bits(bits[i]);
+    float y;
+    switch (which) {
+      case 0: y = sp_exp(x); break;
+      case 1: y = sp_tanh(x); break;
+      case 2: y = sp_gelu(x); break;
+      case 3: y = sp_sigmoid(x); break;
+      case 4: y = sp_log(x); break;
+      default: y = sp_lrelu(x); break;
+    }
+    out_bits[i] = sp_bits(y);
+  }
+  return 0;
+}

@@ -35,6 +35,30 @@ class _Cursor:
         assert self.pos == self.flat.size
 
 
+# ---- probes: tests/regimes.py records named intermediates (layer inputs, activation arguments) to witness which numeric
+# regime a package reaches; with no recording active they cost one comparison
+_probes = None
+
+
+class recording:
+    """with recording() as rec: ... -> rec[name] is the list of arrays probed under that name, in call order."""
+
+    def __enter__(self):
+        global _probes
+        self.prev, _probes = _probes, {}
+        return _probes
+
+    def __exit__(self, *exc):
+        global _probes
+        _probes = self.prev
+
+
+def probe(name, v):
+    if _probes is not None and name is not None:
+        _probes.setdefault(name, []).append(np.array(v, np.float64))
+    return v
+
+
 # ---- MODEL_SPEC 2.1 (mathematical definitions; the float32 polynomial forms approximate these) --------------
 def gelu(x):
     return 0.5 * x * (1.0 + np.tanh(0.7978845608 * (x + 0.044715 * x ** 3)))
@@ -45,39 +69,45 @@ def lrelu(x):
 
 
 def sigmoid(x):
-    return 1.0 / (1.0 + np.exp(-x))
+    with np.errstate(over="ignore"):      # exp(-x) = inf for x < -709: the quotient is the right 0
+        return 1.0 / (1.0 + np.exp(-x))
 
 
 # ---- MODEL_SPEC 3.1 --------------------------------------------------------------------------------------------
-def conv(x, w, b, k, stride=1, dil=1, pre=None):
+def conv(x, w, b, k, stride=1, dil=1, pre=None, name=None):
     """x [T_in][cin] -> [T_in // stride][cout]; output frame t reads input frames (t+1)*stride-1-(k-1-j)*dil,
     frames before the start are zero; weight rows are tap*cin + c."""
     t_in, cin = x.shape
     if pre is not None:
         x = pre(x)
+    probe(name and name + ".in", x)
     t_out = t_in // stride
     y = np.tile(b, (t_out, 1))
     for j in range(k):
         idx = (np.arange(t_out) + 1) * stride - 1 - (k - 1 - j) * dil
         tap = np.where((idx >= 0)[:, None], x[np.clip(idx, 0, None)], 0.0)
+        if j == 0:
+            probe(name and name + ".tap0", tap)      # what the oldest tap reads at each output frame
         y = y + tap @ w[j * cin:(j + 1) * cin]
-    return y
+    return probe(name and name + ".out", y)
 
 
-def conv_transpose(x, w, b, rate, pre):
+def conv_transpose(x, w, b, rate, pre, name=None):
     """ConvT(cin -> cout, rate r) in the spec's polyphase form: Conv(cin -> r*cout, k=2); output frame t*r + rho is
     columns rho*cout .. rho*cout+cout-1 of row t (the bias is stored expanded)."""
-    rows = conv(x, w, b, 2, pre=pre)
+    rows = conv(x, w, b, 2, pre=pre, name=name)
     return rows.reshape(x.shape[0] * rate, -1)
 
 
 # ---- MODEL_SPEC 3.2 --------------------------------------------------------------------------------------------
-def gru(xs, wih, whh, bih, bhh):
+def gru(xs, wih, whh, bih, bhh, name=None):
     hdim = whh.shape[0]
     h = np.zeros(hdim)
     out = []
     for x in xs:
         gi, gh = x @ wih + bih, h @ whh + bhh
+        probe(name and name + ".h.in", h)
+        probe(name and name + ".gate", gi[:2 * hdim] + gh[:2 * hdim])
         r = sigmoid(gi[:hdim] + gh[:hdim])
         z = sigmoid(gi[hdim:2 * hdim] + gh[hdim:2 * hdim])
         n = np.tanh(gi[2 * hdim:] + r * gh[2 * hdim:])
@@ -100,11 +130,12 @@ class PhoneExtractor:
 
     def __call__(self, audio, codebook=None, k=0):
         x = np.asarray(audio, np.float64).reshape(-1, 1)
-        for w, b, ksz, s in self.front:
-            x = gelu(conv(x, w, b, ksz, stride=s))
-        for w, b in self.res:
-            x = x + gelu(conv(x, w, b, 5))
-        x = gru(x, self.wih, self.whh, self.bih, self.bhh) @ self.wo + self.bo
+        for i, (w, b, ksz, s) in enumerate(self.front):
+            x = gelu(conv(x, w, b, ksz, stride=s, name="phone.F%d" % i))
+        for i, (w, b) in enumerate(self.res):
+            x = x + gelu(conv(x, w, b, 5, name="phone.R%d" % i))
+        probe("phone.gru.in", x)
+        x = probe("phone.out.in", gru(x, self.wih, self.whh, self.bih, self.bhh, name="phone.gru")) @ self.wo + self.bo
         if k > 0 and codebook is not None:
             cb = np.asarray(codebook, np.float64)
             d = (cb * cb).sum(1)[None, :] - 2.0 * (x @ cb.T)
@@ -132,20 +163,20 @@ class PitchEstimator:
         audio = np.asarray(audio, np.float64)
         n = audio.size // IN_HOP
         padded = np.concatenate([np.zeros(FFT_N - IN_HOP), audio])
-        frames = np.stack([padded[t * IN_HOP:t * IN_HOP + FFT_N] for t in range(n)]) * self.window
+        frames = probe("pitch.fft.in", np.stack([padded[t * IN_HOP:t * IN_HOP + FFT_N] for t in range(n)]) * self.window)
         spec = np.fft.fft(frames, axis=1)[:, :512]
         feat = 0.5 * np.log(spec.real ** 2 + spec.imag ** 2 + 1e-5)
         x = gelu(conv(feat, *self.p1, 3))
         for w, b in self.res:
             x = x + gelu(conv(x, w, b, 3))
-        h = gru(x, self.wih, self.whh, self.bih, self.bhh)
+        h = gru(x, self.wih, self.whh, self.bih, self.bhh, name="pitch.gru")
         logits = h @ self.wo + self.bo
         lo, hi = max(1, min(BINS - 1, lo)), max(1, min(BINS - 1, hi))
         hi = max(hi, lo)
         bins = lo + np.argmax(logits[:, lo:hi + 1], axis=1)
         e = np.exp(logits - logits.max(1, keepdims=True))
         f0 = e[np.arange(n), bins] / e.sum(1)
-        f1 = 0.1 * np.log((audio.reshape(n, IN_HOP) ** 2).sum(1) / 160.0 + 1e-8)
+        f1 = 0.1 * np.log(probe("pitch.energy.partials", audio.reshape(n, IN_HOP) ** 2).sum(1) / 160.0 + 1e-8)
         f2 = np.clip((bins - np.concatenate([[0], bins[:-1]])) / 8.0, -1.0, 1.0)
         f3 = sigmoid(h @ self.v + self.vb[0])
         return bins, np.stack([f0, f1, f2, f3], axis=1), logits
@@ -183,19 +214,21 @@ class WaveformGenerator:
         for i, (blk, d) in enumerate(zip(self.blocks, (1, 2, 4, 8))):
             keys = kv_raw @ self.kv[i]["k"][0] + self.kv[i]["k"][1]      # [384][256]
             vals = kv_raw @ self.kv[i]["v"][0] + self.kv[i]["v"][1]
-            h = gelu(conv(x, *blk["c1"], 3, dil=d))
-            xa = x + (h @ blk["c2"][0] + blk["c2"][1])
-            q = xa @ blk["q"][0] + blk["q"][1]
+            h = probe("wave.B%d.c2.in" % i, gelu(conv(x, *blk["c1"], 3, dil=d, name="wave.B%d.c1" % i)))
+            xa = probe("wave.B%d.q.in" % i, x + (h @ blk["c2"][0] + blk["c2"][1]))
+            q = probe("wave.B%d.att.q" % i, xa @ blk["q"][0] + blk["q"][1])
+            probe("wave.B%d.att.k" % i, keys)
             s = (q @ keys.T) * 0.0625
-            p = np.exp(s - s.max(1, keepdims=True))
-            o = (p @ vals) / p.sum(1, keepdims=True)
+            p = np.exp(probe("wave.B%d.att.s" % i, s - s.max(1, keepdims=True)))
+            probe("wave.B%d.att.v" % i, vals)
+            o = probe("wave.B%d.o.in" % i, (p @ vals) / p.sum(1, keepdims=True))
             x = xa + (o @ blk["o"][0] + blk["o"][1])
         y = x
-        for st in self.up:
-            y = conv_transpose(y, *st["t"], st["r"], pre=lrelu)
-            y = y + conv(y, *st["a"], 3, dil=1, pre=lrelu)
-            y = y + conv(y, *st["b"], 3, dil=3, pre=lrelu)
-        return np.tanh(conv(y, self.wfin, self.bfin, 7, pre=lrelu))[:, 0]
+        for j, st in enumerate(self.up):
+            y = conv_transpose(y, *st["t"], st["r"], pre=lrelu, name="wave.U%d.t" % j)
+            y = y + conv(y, *st["a"], 3, dil=1, pre=lrelu, name="wave.U%d.a" % j)
+            y = y + conv(y, *st["b"], 3, dil=3, pre=lrelu, name="wave.U%d.b" % j)
+        return np.tanh(conv(y, self.wfin, self.bfin, 7, pre=lrelu, name="wave.fin"))[:, 0]
 
 
 # ---- MODEL_SPEC 6.3: the waveform generator of the legacy generations ------------------------------------------------
@@ -217,15 +250,15 @@ class LegacyWaveformGenerator:
         phone, feat = np.asarray(phone, np.float64), np.asarray(feat, np.float64)
         e = (self.pitch_emb[np.asarray(bins)] + feat @ self.wf) + np.asarray(speaker, np.float64)
         x = (phone @ self.wi + self.bi) + e
-        for blk, d in zip(self.blocks, (1, 2, 4, 8)):
-            h = gelu(conv(x, *blk["c1"], 3, dil=d))
+        for i, (blk, d) in enumerate(zip(self.blocks, (1, 2, 4, 8))):
+            h = probe("wave.B%d.c2.in" % i, gelu(conv(x, *blk["c1"], 3, dil=d, name="wave.B%d.c1" % i)))
             x = x + (h @ blk["c2"][0] + blk["c2"][1])
         y = x
-        for st in self.up:
-            y = conv_transpose(y, *st["t"], st["r"], pre=lrelu)
-            y = y + conv(y, *st["a"], 3, dil=1, pre=lrelu)
-            y = y + conv(y, *st["b"], 3, dil=3, pre=lrelu)
-        return np.tanh(conv(y, self.wfin, self.bfin, 7, pre=lrelu))[:, 0]
+        for j, st in enumerate(self.up):
+            y = conv_transpose(y, *st["t"], st["r"], pre=lrelu, name="wave.U%d.t" % j)
+            y = y + conv(y, *st["a"], 3, dil=1, pre=lrelu, name="wave.U%d.a" % j)
+            y = y + conv(y, *st["b"], 3, dil=3, pre=lrelu, name="wave.U%d.b" % j)
+        return np.tanh(conv(y, self.wfin, self.bfin, 7, pre=lrelu, name="wave.fin"))[:, 0]
 
 
 def read_rows(path):

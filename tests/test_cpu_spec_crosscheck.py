@@ -9,7 +9,7 @@ import pytest
 
 import spec_numpy as sn
 
-HOPS = 14
+HOPS = 24     # more than 16: wave block 3 (k3, dilation 8) reads 16 frames back, and in a shorter run that tap only ever sees the zero prefix
 
 
 @pytest.fixture(scope="module")
@@ -72,7 +72,12 @@ def test_waveform_generator_matches_independent_restatement(driven, model_dir):
     wg = sn.WaveformGenerator(model_dir)
     for k in (0, 3):
         r = rec[k]
-        want = wg(r["phone"], r["q"], r["feat"], tables.additive[1], tables.formant[6], tables.kv[1])
+        with sn.recording() as probes:
+            want = wg(r["phone"], r["q"], r["feat"], tables.additive[1], tables.formant[6], tables.kv[1])
+        oldest = probes["wave.B3.c1.tap0"][0]           # [frames][256]: what the restatement's conv read through block 3's oldest tap
+        x3 = probes["wave.B3.c1.in"][0]
+        assert np.all(oldest[:16] == 0) and np.abs(oldest[16:]).max() > 0.1, "block 3's 16-frames-back tap never read a real frame"
+        assert np.array_equal(oldest[16:], x3[:HOPS - 16]), "block 3's oldest tap lies 16 frames back"
         dev = float(np.abs(r["pcm"] - want).max())
         print("waveform (k=%d): max-abs %.3g, rms %.3g" % (k, dev, np.sqrt((want ** 2).mean())))
         assert np.sqrt((want ** 2).mean()) > 0.02

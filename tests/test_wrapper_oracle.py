@@ -77,6 +77,30 @@ def test_chain_matches_reference_live(wo, ref, sr, block):
     assert np.array_equal(want, b), "max-abs %g" % np.abs(want - b).max()
 
 
+VANISHING_CASES = [(44100, 441), (48000, 480), (16000, 333)]
+
+
+@pytest.mark.parametrize("sr,block", VANISHING_CASES)
+def test_vanishing_chain_matches_reference_live(wo, ref, sr, block):
+    """A signal that decays through the subnormal range and returns, input gain -30 dB, output gain moving to -60 dB across the decay
+    (MODEL_SPEC 2.5: nothing is flushed): the wrapper oracle against the reference's own gain.h / resample.h, live where
+    oracle/_ref is built, and always against its outputs as recorded in golden/wrapper_vanishing.npz."""
+    n = int(0.12 * sr)
+    x = wrapperlib.vanishing_signal(n, sr, seed=2000 + sr)
+    ev_in, ev_out = wrapperlib.vanishing_gain_events(n)
+    tiny = np.abs(x[(x != 0)])
+    assert (tiny < 2.0 ** -126).sum() > 0.1 * n and (x == 0).any() and np.abs(x[-n // 4:]).max() > 0.1
+    want = np.load(os.path.join(GOLD, "wrapper_vanishing.npz"))["chain_%d_%d" % (sr, block)]
+    if ref is not None:
+        a = ref.run_chain(sr, x, block, in_gain_events=ev_in, out_gain_events=ev_out)
+        assert np.array_equal(a, want), "recording out of date: max-abs %g" % np.abs(a - want).max()
+    b = wo.run_chain(sr, x, block, in_gain_events=ev_in, out_gain_events=ev_out)
+    assert np.array_equal(want, b), "max-abs %g" % np.abs(want - b).max()
+    out_tiny = np.abs(want[want != 0])
+    assert (out_tiny < 2.0 ** -126).sum() > 0.05 * n, "the output passes through the subnormal range too"
+    assert np.abs(want).max() > 1e-3
+
+
 def test_dc_gain_is_half(wo):
     """Zero-stuffing 240 -> 480 has no make-up gain, so DC through an identity-like hop comes out at 0.5
     (SURVEY.md appendix A.3)."""

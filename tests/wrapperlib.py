@@ -101,3 +101,18 @@ def test_signal(n, sample_rate, seed):
     f0, f1 = 60.0, min(9000.0, 0.45 * sample_rate)
     phase = 2 * np.pi * (f0 * t + 0.5 * (f1 - f0) * t * t / max(t[-1], 1e-9))
     return (0.25 * np.sin(phase) + 0.25 * noise).astype(np.float32)
+
+
+def vanishing_signal(n, sample_rate, seed):
+    """test_signal under an envelope that starts at 1e-30, decays through the whole subnormal range to below 1e-44 (nothing but 0 left
+    in float32) over the first 45 % of the run, comes back to 0.3 by 70 % and stays: a tail fading out and a new note."""
+    x = test_signal(n, sample_rate, seed).astype(np.float64) / 0.5
+    t = np.arange(n) / float(n)
+    top = np.log10(0.3)
+    log_env = np.where(t < 0.45, -30.0 - 16.5 * t / 0.45, np.where(t < 0.7, -46.5 + (top + 46.5) * (t - 0.45) / 0.25, top))
+    return (x * 10.0 ** log_env).astype(np.float32)
+
+
+def vanishing_gain_events(n):
+    """input gain -30 dB from the start; output gain from 0 dB towards -60 dB from the start of the decay, back to 0 dB with the note"""
+    return [(0, -30.0)], [(0, -60.0), (int(0.6 * n), 0.0)]

@@ -118,6 +118,15 @@ def reference_cases():
         m.close()
     np.savez_compressed(os.path.join(GOLD, "reference_cases.npz"), **g)
     print("reference_cases.npz %d bytes, %d arrays" % (os.path.getsize(os.path.join(GOLD, "reference_cases.npz")), len(g)))
+    # wrapper_vanishing.npz: tests/test_wrapper_oracle.py::test_vanishing_chain_matches_reference_live
+    v = {}
+    for sr, block in test_wrapper_oracle.VANISHING_CASES:
+        n = int(0.12 * sr)
+        ev_in, ev_out = wrapperlib.vanishing_gain_events(n)
+        v["chain_%d_%d" % (sr, block)] = ref.run_chain(sr, wrapperlib.vanishing_signal(n, sr, seed=2000 + sr), block,
+                                                       in_gain_events=ev_in, out_gain_events=ev_out)
+    np.savez_compressed(os.path.join(GOLD, "wrapper_vanishing.npz"), **v)
+    print("wrapper_vanishing.npz %d bytes, %d arrays" % (os.path.getsize(os.path.join(GOLD, "wrapper_vanishing.npz")), len(v)))
 
 
 if __name__ == "__main__":
