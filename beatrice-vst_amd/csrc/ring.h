@@ -22,10 +22,13 @@ struct Ring {
 // so every wait for an LDS operand (s_waitcnt lgkmcnt(0): flat and LDS results return out of order) also waits for every
 // weight prefetch in flight.  A round trip through address space 1 tells the compiler what it is (InferAddressSpaces then
 // emits global_load / global_store with their own counter and the ISA shows the intended `s_waitcnt vmcnt(8) lgkmcnt(7)`).
-// MEASURED (round 4, same box, A/B): the tick launch is 4 % SLOWER with it (69.2 vs 66.5 us at 256 streams, 241 vs 232 us at
-// 1 024) -- VGPR spills 48 -> 112 in the table kernel, and the launch is bound by ALU issue, not by exposed latency.  The
-// helpers stay for kernels that take pointers from memory and ARE latency-bound; fuse::run_type uses them only under
-// -DFUSE_GLOBALIZE.
+// MEASURED (round 4, same box, A/B) for EVERY pointer of EVERY body (globalize() below, -DFUSE_GLOBALIZE): the tick launch is
+// 4 % SLOWER with it (69.2 vs 66.5 us at 256 streams, 241 vs 232 us at 1 024) -- VGPR spills 48 -> 112 in the table kernel.
+// That switch stays off.  The NARROW form is on: only the weight stream and the row gather of the GEMM bodies' segment loops
+// (rowchain.hip.h rc::WGlobal, load_tile, conv_rows_body's load_seg) go through as_global, inside the bodies themselves.  Their
+// bases are wave-uniform, so the loads are global_load off a SCALAR base with a 32-bit lane offset: no VGPR pair per column
+// tile, the base advanced by scalar adds, a counted vmcnt wait per k-block, and LDS waits that leave the prefetch in flight.
+// Same-box A/B at 256 streams x 4 hops: 234.6 -> 224.4 us per tick launch, spills 241 -> 231 (profiles/weight_stream_notes.md).
 // (A plain generic -> global -> generic cast is folded away by the front end; the empty asm between the two casts keeps it.
 //  "s": the pointer is wave-uniform and stays in scalar registers -- as_global_v for a pointer that may differ between lanes.)
 template <class T>
@@ -52,15 +55,16 @@ __host__ __device__ inline size_t ring_stream_floats(const Ring& r) { return (si
 // first new frame of hop `hop`
 __device__ __forceinline__ int ring_pos(const Ring& r, int hop) { return (hop % r.m) * r.n; }
 
-// pointer to frame (pos + rel) of stream b; rel in [-history, n)
-__device__ __forceinline__ float* ring_frame(const Ring& r, int b, int pos, int rel) {
+// frame (pos + rel) of stream b; rel in [-history, n): its first float's index from the ring's base, and the pointer to it
+__device__ __forceinline__ unsigned ring_index(const Ring& r, int b, int pos, int rel) {
   int f = pos + rel;
   const int R = r.n * r.m;
   if (f < 0) f += R;
   // 32-bit index arithmetic (a ring holds fewer than 2^32 floats: RingArena::build refuses larger ones): the 64-bit form cost
   // six to eight VALU instructions per call, and epilogues call this once per output element
-  return r.base + (unsigned)(b * R + f) * (unsigned)r.C;
+  return (unsigned)(b * R + f) * (unsigned)r.C;
 }
+__device__ __forceinline__ float* ring_frame(const Ring& r, int b, int pos, int rel) { return r.base + ring_index(r, b, pos, rel); }
 
 // The step counter a kernel works on, and the slot of resident I/O buffers that belongs to it.  Ordinary launches read
 // the pair from device memory (args.hop); in the batch's tick launch (tick.hip.h) the table kernel takes every stage's

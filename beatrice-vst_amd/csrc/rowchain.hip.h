@@ -117,28 +117,76 @@ __device__ __forceinline__ void pin_pipeline() {
 #ifndef RC_PREFETCH
 #define RC_PREFETCH 8
 #endif
+// Where a wavefront's weight fragments come from.  A fragment's address is WAVE-UNIFORM (layer, column tile, k-block) plus lane x 16
+// bytes, and the segment loops take it in exactly that form (WGlobal): the uniform base as a GLOBAL pointer in scalar registers
+// (ring.h as_global), the lane's part as one 32-bit byte offset shared by every column tile.  The loads are then global_load off a
+// scalar base -- their own counter (vmcnt), so the wait in front of an LDS operand leaves the prefetch in flight and the wait in
+// front of a fragment is a COUNTED one that leaves D - 1 k-blocks outstanding; the base advances with scalar adds instead of a
+// 64-bit VALU add per column tile.  WLane is the earlier form, a per-lane generic pointer: flat loads wherever the pointer came
+// from a table in device memory (the tick launch), which count on the LDS counter too.  -DRC_WSTREAM_GLOBAL=0 builds the product
+// with it (A/B); tools/microbench/seg_loop.hip runs both.
+#ifndef RC_WSTREAM_GLOBAL
+#define RC_WSTREAM_GLOBAL 1
+#endif
+struct WLane {
+  const float4* p;   // this lane's float4 of k-block 0
+  // `u`: the WAVE-UNIFORM address of the record of k-block 0 (lane 0's float4)
+  __device__ static __forceinline__ WLane make(const float4* u, const int lane) { return WLane{u + lane}; }
+  __device__ __forceinline__ WLane at(const size_t f4) const { return WLane{p + f4}; }   // f4: a uniform distance in float4
+  __device__ __forceinline__ float4 kblock(const int kb) const { return p[(size_t)kb * 64]; }
+};
+struct WGlobal {
+  typedef __attribute__((address_space(1))) const char gbyte;
+  gbyte* base;     // wave-uniform, scalar registers
+  unsigned voff;   // lane x 16
+  __device__ static __forceinline__ WGlobal make(const float4* u, const int lane) {
+    return WGlobal{(gbyte*)reinterpret_cast<const char*>(as_global(u)), (unsigned)lane * 16u};
+  }
+  __device__ __forceinline__ WGlobal at(const size_t f4) const { return WGlobal{base + f4 * 16, voff}; }
+  // Eight k-blocks (8 KiB) share one scalar base: the load's 13-bit signed immediate reaches -4096 .. +3072 around it.  The empty
+  // asm keeps that base a scalar value of its own -- left to itself the compiler folds "base + lane offset" into ONE 64-bit VGPR
+  // pair and advances THAT with a v_add_co / v_addc pair per column tile and four k-blocks, which is what this form removes.
+  __device__ __forceinline__ float4 kblock(const int kb) const {
+    gbyte* q = base + ((size_t)(kb & ~7) * 1024 + 4096);
+    asm("" : "+s"(q));
+    const f32x4 v = *reinterpret_cast<__attribute__((address_space(1))) const f32x4*>(q + (size_t)voff + ((kb & 7) * 1024 - 4096));
+    return make_float4(v[0], v[1], v[2], v[3]);
+  }
+};
+#if RC_WSTREAM_GLOBAL
+using WStream = WGlobal;
+#else
+using WStream = WLane;
+#endif
+// the hook a caller hands a segment loop to issue loads of its own (conv_rows_body: the next segment's row gather) right behind
+// the segment's prologue fragments: vector loads return in order, so a gather issued BEFORE them would have to be complete at the
+// loop's first fragment wait, while behind them it has D k-blocks of MFMAs as cover and its wait stays the one in front of its use
+struct NoGather { __device__ __forceinline__ void operator()() const {} };
 // prefetch depth of a segment in k-blocks (registers: D * CG float4)
 template <int RT, int CG> __host__ __device__ constexpr int seg_depth() { return RT == 1 ? (CG <= 2 ? RC_PREFETCH : (CG <= 3 ? 4 : 2)) : (RT * CG <= 2 ? 8 : 4); }
 // the first seg_depth() k-blocks of a segment's weight fragments, requested by the CALLER ahead of time (a body's first segment: the
 // request goes out before the body gathers its rows, so that the two round trips overlap instead of following each other)
 template <int RT, int CG> struct SegHead { float4 v[seg_depth<RT, CG>()][CG]; };
-template <int RT, int CG>
-__device__ __forceinline__ void seg_head_load(SegHead<RT, CG>& h, const float4* const (&wf)[CG]) {
+template <int RT, int CG, class W>
+__device__ __forceinline__ void seg_head_load(SegHead<RT, CG>& h, const W (&wf)[CG]) {
 #pragma unroll
   for (int d = 0; d < seg_depth<RT, CG>(); ++d)
 #pragma unroll
-    for (int c = 0; c < CG; ++c) h.v[d][c] = wf[c][(size_t)d * 64];
+    for (int c = 0; c < CG; ++c) h.v[d][c] = wf[c].kblock(d);
 }
-template <int CG, int KB, bool HEAD = false>
-__device__ __forceinline__ void mma_segment_p(f32x4 (&acc)[CG], const float* __restrict__ a, const float4* const (&wf)[CG], const SegHead<1, CG>* head = nullptr) {
-  constexpr int D = seg_depth<1, CG>();
+// (D: the prefetch depth, seg_depth() in the product; a parameter for tools/microbench/seg_loop.hip's sweep)
+template <int CG, int KB, bool HEAD = false, int D = seg_depth<1, CG>(), class W, class Gather = NoGather>
+__device__ __forceinline__ void mma_segment_p(f32x4 (&acc)[CG], const float* __restrict__ a, const W (&wf)[CG], const SegHead<1, CG>* head = nullptr,
+                                              Gather gather = Gather()) {
   static_assert(KB % D == 0, "segment length");
+  static_assert(!HEAD || D == seg_depth<1, CG>(), "a SegHead holds seg_depth() k-blocks");
   float4 bq[D][CG];
   pin_pipeline();   // (the segment's first loads stay behind what precedes it: hoisted over an epilogue they only add register pressure)
 #pragma unroll
   for (int d = 0; d < D; ++d)
 #pragma unroll
-    for (int c = 0; c < CG; ++c) { if constexpr (HEAD) bq[d][c] = head->v[d][c]; else bq[d][c] = wf[c][(size_t)d * 64]; }
+    for (int c = 0; c < CG; ++c) { if constexpr (HEAD) bq[d][c] = head->v[d][c]; else bq[d][c] = wf[c].kblock(d); }
+  gather();
   float4 an = lds_kblock(a, 0);   // activations of the k-block to come (one k-block ahead: LDS latency behind 4 CG MFMAs), one ds_read_b128
 #pragma unroll
   for (int kb = 0; kb < KB; kb += D) {
@@ -150,7 +198,7 @@ __device__ __forceinline__ void mma_segment_p(f32x4 (&acc)[CG], const float* __r
       const float4 x = an;
       if (kb + d + D < KB) {
 #pragma unroll
-        for (int c = 0; c < CG; ++c) bq[d][c] = wf[c][(size_t)ABL_KB(kb + d + D) * 64];
+        for (int c = 0; c < CG; ++c) bq[d][c] = wf[c].kblock(ABL_KB(kb + d + D));
       }
       if (kb + d + 1 < KB) an = lds_kblock(a, kb + d + 1);
       pin_pipeline();
@@ -167,17 +215,18 @@ __device__ __forceinline__ void mma_segment_p(f32x4 (&acc)[CG], const float* __r
 }
 // The same for RT row tiles of 16 that share every B fragment (a1 = a0 + one LDS tile): acc[t][c] += A_t . W_c.
 // A fragment then feeds RT MFMAs: half the weight traffic per multiply-add at RT = 2.
-template <int RT, int CG, int KB, bool HEAD = false>
+template <int RT, int CG, int KB, bool HEAD = false, int D = seg_depth<RT, CG>(), class W, class Gather = NoGather>
 __device__ __forceinline__ void mma_segment_rt(f32x4 (&acc)[RT][CG], const float* __restrict__ a, const int a_tile_stride,
-                                               const float4* const (&wf)[CG], const SegHead<RT, CG>* head = nullptr) {
-  constexpr int D = seg_depth<RT, CG>();
+                                               const W (&wf)[CG], const SegHead<RT, CG>* head = nullptr, Gather gather = Gather()) {
   static_assert(KB % D == 0, "segment length");
+  static_assert(!HEAD || D == seg_depth<RT, CG>(), "a SegHead holds seg_depth() k-blocks");
   float4 bq[D][CG];
   pin_pipeline();
 #pragma unroll
   for (int d = 0; d < D; ++d)
 #pragma unroll
-    for (int c = 0; c < CG; ++c) { if constexpr (HEAD) bq[d][c] = head->v[d][c]; else bq[d][c] = wf[c][(size_t)d * 64]; }
+    for (int c = 0; c < CG; ++c) { if constexpr (HEAD) bq[d][c] = head->v[d][c]; else bq[d][c] = wf[c].kblock(d); }
+  gather();
   float4 an[RT];
 #pragma unroll
   for (int t = 0; t < RT; ++t) an[t] = lds_kblock(a + t * a_tile_stride, 0);
@@ -193,7 +242,7 @@ __device__ __forceinline__ void mma_segment_rt(f32x4 (&acc)[RT][CG], const float
       for (int t = 0; t < RT; ++t) av[t] = an[t];
       if (kb + d + D < KB) {
 #pragma unroll
-        for (int c = 0; c < CG; ++c) bq[d][c] = wf[c][(size_t)ABL_KB(kb + d + D) * 64];
+        for (int c = 0; c < CG; ++c) bq[d][c] = wf[c].kblock(ABL_KB(kb + d + D));
       }
       if (kb + d + 1 < KB) {
 #pragma unroll
@@ -219,12 +268,12 @@ __device__ __forceinline__ void mma_segment_rt(f32x4 (&acc)[RT][CG], const float
     }
   }
 }
-template <int CG, int KB>
-__device__ __forceinline__ void mma_segment(f32x4 (&acc)[CG], const float* __restrict__ a, const float4* __restrict__ wf,
-                                            const size_t tile_stride) {
-  const float4* wfc[CG];
+// (`wf`: column tile 0 at the segment's first k-block; consecutive column tiles of the wavefront `tile_stride` float4 apart)
+template <int CG, int KB, class W>
+__device__ __forceinline__ void mma_segment(f32x4 (&acc)[CG], const float* __restrict__ a, const W& wf, const size_t tile_stride) {
+  W wfc[CG];
 #pragma unroll
-  for (int c = 0; c < CG; ++c) wfc[c] = wf + c * tile_stride;
+  for (int c = 0; c < CG; ++c) wfc[c] = wf.at(c * tile_stride);
   mma_segment_p<CG, KB>(acc, a, wfc);
 }
 
@@ -235,7 +284,7 @@ template <int NSEG, int CG, class Epi4>
 __device__ __forceinline__ void layer256(const float* const (&seg)[NSEG], const int as, const float* __restrict__ w_packed,
                                          const int wave, const int lane, Epi4 epi4) {
   constexpr int K = NSEG * 256;
-  const float4* wf = reinterpret_cast<const float4*>(w_packed) + (size_t)wave * (K / 16) * 64 + lane;
+  const WStream wf = WStream::make(reinterpret_cast<const float4*>(w_packed) + (size_t)wave * (K / 16) * 64, lane);
   const size_t tile_stride = (size_t)NWAVE * (K / 16) * 64;
   f32x4 tot[CG];
 #pragma unroll
@@ -243,7 +292,7 @@ __device__ __forceinline__ void layer256(const float* const (&seg)[NSEG], const 
     f32x4 acc[CG];
 #pragma unroll
     for (int c = 0; c < CG; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    mma_segment<CG, 16>(acc, seg[s] + (lane & 15) * as + lane_koff(lane), wf + (size_t)s * 16 * 64, tile_stride);
+    mma_segment<CG, 16>(acc, seg[s] + (lane & 15) * as + lane_koff(lane), wf.at((size_t)s * 16 * 64), tile_stride);
 #pragma unroll
     for (int c = 0; c < CG; ++c) {
       if (s == 0) tot[c] = acc[c];
@@ -261,6 +310,7 @@ __device__ __forceinline__ void layer256(const float* const (&seg)[NSEG], const 
 template <int HOPS = 1>
 __device__ __forceinline__ void load_tile(float* __restrict__ dst, const Ring& ring, const int* sid /* LDS, [16] */, const int pos, const int rel,
                                           const int tid, const int* rowhop = nullptr) {
+  const float* gbase = as_global(ring.base);   // (the ring's base is uniform: a global load off a scalar base, ring.h)
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int idx = tid + i * NTHR;
@@ -268,7 +318,7 @@ __device__ __forceinline__ void load_tile(float* __restrict__ dst, const Ring& r
     piece_of<4>(idx >> 6, idx & 63, &r, &q);
     const int b = sid[r];
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (b >= 0) v = *reinterpret_cast<const float4*>(ring_frame(ring, b / HOPS, rowhop != nullptr ? ring_pos(ring, rowhop[r]) : pos, rel + b % HOPS) + 4 * q);
+    if (b >= 0) v = *reinterpret_cast<const float4*>(gbase + (ring_index(ring, b / HOPS, rowhop != nullptr ? ring_pos(ring, rowhop[r]) : pos, rel + b % HOPS) + 4u * (unsigned)q));
     store_perm4(dst + r * AS, 4 * q, v.x, v.y, v.z, v.w);
   }
 }
@@ -436,12 +486,12 @@ __device__ __forceinline__ void block_b_body(const BlockBArgs& a, const int g, f
   __syncthreads();
   RC_STAMP(4);
   {  // o = (segment 0 + segment 1) * (1 / sum): K = 384 = 256 + 128, V packed [384][256]
-    const float4* wf = reinterpret_cast<const float4*>(a.v + (size_t)slot * B_KV_LEN * B_HID) + (size_t)wave * (B_KV_LEN / 16) * 64 + lane;
+    const WStream wf = WStream::make(reinterpret_cast<const float4*>(a.v + (size_t)slot * B_KV_LEN * B_HID) + (size_t)wave * (B_KV_LEN / 16) * 64, lane);
     const size_t tile_stride = (size_t)NWAVE * (B_KV_LEN / 16) * 64;
     const float* ap = S + (lane & 15) * SS + lane_koff(lane);
     f32x4 acc0[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, acc1[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     mma_segment<2, 16>(acc0, ap, wf, tile_stride);
-    mma_segment<2, 8>(acc1, ap + 256, wf + (size_t)16 * 64, tile_stride);
+    mma_segment<2, 8>(acc1, ap + 256, wf.at((size_t)16 * 64), tile_stride);
     const int r = lane & 15;
     const float ir = inv[r];
 #pragma unroll
@@ -709,11 +759,11 @@ __device__ __forceinline__ void conv_rows_body(const ConvArgs& a, const int bx, 
   if (hop < 0) return;
   // the first thing a workgroup does: request the first weight fragments of its first segment -- that round trip then runs beside the
   // row table's barrier and the row gather instead of behind them (a short body is mostly such round trips, profiles/r05_notes.md)
-  const float4* wfc[CG];
+  WStream wfc[CG];
 #pragma unroll
   for (int c = 0; c < CG; ++c) {
     const int nt = wave + NWAVE * c < NTL ? wave + NWAVE * c : NTL - 1;  // surplus tiles of a ragged layer recompute the last one
-    wfc[c] = reinterpret_cast<const float4*>(a.w) + (size_t)(nt_base + nt) * (K / 16) * 64 + lane;
+    wfc[c] = WStream::make(reinterpret_cast<const float4*>(a.w) + (size_t)(nt_base + nt) * (K / 16) * 64, lane);
   }
 #ifndef RC_SEG_HEAD
 #define RC_SEG_HEAD 0   // A/B switch, OFF: 1 = the first segment's first weight fragments requested before the row gather -- measured 256 streams x 2 hops 118.1 -> 120.5 us (slower), x 4 hops 237.4 -> 236.4, x 1 hop unchanged (profiles/r05_notes.md)
@@ -740,6 +790,7 @@ __device__ __forceinline__ void conv_rows_body(const ConvArgs& a, const int bx, 
     pb[i] = rb_[pr[i]]; pt[i] = rb_[ROWS + pr[i]];
   }
   float4 nx[2 * RT];
+  const float* in_base = as_global(a.in.base);   // (uniform: the gather is global loads off a scalar base with 32-bit offsets, ring.h)
   auto load_seg = [&](int s) {
 #pragma unroll
     for (int i = 0; i < 2 * RT; ++i) {
@@ -748,8 +799,8 @@ __device__ __forceinline__ void conv_rows_body(const ConvArgs& a, const int bx, 
       const int j = live ? kk / L::CIN : 0, c = live ? kk % L::CIN : 0;
       nx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (live && pb[i] >= 0)
-        nx[i] = *reinterpret_cast<const float4*>(ring_frame(a.in, pb[i], rag ? ring_pos(a.in, rb_[2 * ROWS + pr[i]]) : pos_in,   // (ragged: worked out per load, no register held for it in the common case)
-                                                            (pt[i] + 1) * L::STRIDE - 1 - (L::KSZ - 1 - j) * L::DIL + a.rel_shift) + c);
+        nx[i] = *reinterpret_cast<const float4*>(in_base + (ring_index(a.in, pb[i], rag ? ring_pos(a.in, rb_[2 * ROWS + pr[i]]) : pos_in,   // (ragged: worked out per load, no register held for it in the common case)
+                                                                       (pt[i] + 1) * L::STRIDE - 1 - (L::KSZ - 1 - j) * L::DIL + a.rel_shift) + (unsigned)c));
     }
   };
   auto store_seg = [&](float* dst) {
@@ -766,30 +817,31 @@ __device__ __forceinline__ void conv_rows_body(const ConvArgs& a, const int bx, 
   f32x4 tot[RT][CG];
 #pragma unroll
   for (int s = 0; s < P; ++s) {
-    if (s + 1 < P) load_seg(s + 1);
+    // the next segment's gather goes out from INSIDE the loop, behind the segment's prologue fragments (NoGather above)
+    auto gather = [&] { if (s + 1 < P) load_seg(s + 1); };
     f32x4 acc[RT][CG];
 #pragma unroll
     for (int t = 0; t < RT; ++t)
 #pragma unroll
       for (int c = 0; c < CG; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float4* wfs[CG];
+    WStream wfs[CG];
 #pragma unroll
-    for (int c = 0; c < CG; ++c) wfs[c] = wfc[c] + (size_t)s * 16 * 64;
+    for (int c = 0; c < CG; ++c) wfs[c] = wfc[c].at((size_t)s * 16 * 64);
     const float* ap = slot[s & 1] + (lane & 15) * AS + lane_koff(lane);
     if (RC_SEG_HEAD != 0 && s == 0) {   // (s is a compile-time index after unrolling)
       if constexpr (RT == 1) {
-        if constexpr (P > 1) mma_segment_p<CG, 16, true>(acc[0], ap, wfs, &head);
-        else mma_segment_p<CG, LAST / 16, true>(acc[0], ap, wfs, &head);
+        if constexpr (P > 1) mma_segment_p<CG, 16, true>(acc[0], ap, wfs, &head, gather);
+        else mma_segment_p<CG, LAST / 16, true>(acc[0], ap, wfs, &head, gather);
       } else {
-        if constexpr (P > 1) mma_segment_rt<RT, CG, 16, true>(acc, ap, TILE, wfs, &head);
-        else mma_segment_rt<RT, CG, LAST / 16, true>(acc, ap, TILE, wfs, &head);
+        if constexpr (P > 1) mma_segment_rt<RT, CG, 16, true>(acc, ap, TILE, wfs, &head, gather);
+        else mma_segment_rt<RT, CG, LAST / 16, true>(acc, ap, TILE, wfs, &head, gather);
       }
     } else if constexpr (RT == 1) {
-      if (s + 1 < P) mma_segment_p<CG, 16>(acc[0], ap, wfs);
-      else mma_segment_p<CG, LAST / 16>(acc[0], ap, wfs);
+      if (s + 1 < P) mma_segment_p<CG, 16>(acc[0], ap, wfs, nullptr, gather);
+      else mma_segment_p<CG, LAST / 16>(acc[0], ap, wfs, nullptr, gather);
     } else {
-      if (s + 1 < P) mma_segment_rt<RT, CG, 16>(acc, ap, TILE, wfs);
-      else mma_segment_rt<RT, CG, LAST / 16>(acc, ap, TILE, wfs);
+      if (s + 1 < P) mma_segment_rt<RT, CG, 16>(acc, ap, TILE, wfs, nullptr, gather);
+      else mma_segment_rt<RT, CG, LAST / 16>(acc, ap, TILE, wfs, nullptr, gather);
     }
 #pragma unroll
     for (int t = 0; t < RT; ++t)
