@@ -424,6 +424,9 @@ _BATCH = {
     "BeatriceBatch_ResetStream": (C.c_int, [_vp, C.c_int]),
     "BeatriceBatch_ResetStreamInFlight": (C.c_int, [_vp, C.c_int]),
     "BeatriceBatch_TicksLaunched": (C.c_longlong, [_vp]),
+    "BeatriceBatch_StreamBlobBytes": (C.c_size_t, [_vp]),
+    "BeatriceBatch_ExportStreams": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
+    "BeatriceBatch_ImportStreams": (C.c_int, [_vp, C.c_int, _i32p, _vp, _i32p, C.c_int]),
     "BeatriceBatch_ConvertFrames": (C.c_int, [_vp, _f32p, _f32p]),
     "BeatriceBatch_ConvertFramesDevice": (C.c_int, [_vp, _vp, _vp]),
     "BeatriceBatch_ConvertBlocks48k": (C.c_int, [_vp, _f32p, _f32p, C.c_int]),
@@ -555,6 +558,29 @@ class Batch:
             nm = names.raw[64 * i:64 * (i + 1)].split(b"\0")[0].decode()
             rows.append(dict(name=nm, launches=launches[i], mean_us=us[i], flops=fl[i], bytes=by[i]))
         return rows
+
+    def stream_blob_bytes(self):
+        """Bytes of one stream's blob (the same for every stream of this batch)."""
+        return int(self.a.BeatriceBatch_StreamBlobBytes(self.h))
+
+    def export_streams(self, streams):
+        """The state and settings of `streams` as len(streams) blobs back to back (BeatriceBatch_ExportStreams): bytes that
+        import_streams of another batch of the same library build and hops per step takes.  Drains; changes nothing."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        buf = C.create_string_buffer(max(1, len(idx) * self.stream_blob_bytes()))
+        self._check(self.a.BeatriceBatch_ExportStreams(self.h, len(idx), iptr(idx), C.cast(buf, _vp)))
+        return buf.raw[:len(idx) * self.stream_blob_bytes()]
+
+    def import_streams(self, streams, blobs, entry_map=None):
+        """Blob i of `blobs` (export_streams' bytes) becomes stream streams[i] of this batch (BeatriceBatch_ImportStreams).
+        entry_map[i]: the table entry of this batch that holds what entry i of the source batch held (None: the same entries)."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if len(blobs) != len(idx) * self.stream_blob_bytes():
+            raise ValueError("import_streams: %d bytes for %d streams of %d bytes each" % (len(blobs), len(idx), self.stream_blob_bytes()))
+        em = None if entry_map is None else np.ascontiguousarray(entry_map, np.int32).reshape(-1)
+        buf = C.create_string_buffer(bytes(blobs), max(1, len(blobs)))
+        self._check(self.a.BeatriceBatch_ImportStreams(self.h, len(idx), iptr(idx), C.cast(buf, _vp),
+                                                       None if em is None else iptr(em), 0 if em is None else len(em)))
 
     def close(self):
         if self.h:

@@ -24,6 +24,7 @@
 #include "abi_objects.h"
 #include "batch_modes.h"
 #include "beatrice_batch.h"
+#include "stream_blob.h"
 #include "tick.hip.h"
 #include "wrapper.hip.h"
 
@@ -157,6 +158,15 @@ struct BeatriceBatch {
   std::vector<int> row_slot[B_NBLOCKS];  // [B*H] K/V slot of attention row (stream, hop in step)
   bool kv_transient = false;  // rows of the last step's early hops still hold pre-switch slots (H > 1)
   bool vq_dirty = true;   // a VQ setting changed since the k-NN launch was last (de)selected
+  // BeatriceBatch_ExportStreams / ImportStreams (stream_blob.h, stream_blob.hip): the blob's layout, fixed when the batch is created; the
+  // piece table and the staging pair -- pinned host and device, `cap` = min(n, 16) blobs each -- are made by the first call that needs them
+  struct StreamBlobs {
+    sblob::Layout layout;
+    DevBuf<BlobPiece> d_pieces;
+    int n_pieces = 0, cap = 0;
+    PinnedBuf<unsigned char> h_stage;
+    DevBuf<unsigned char> d_stage;
+  } sb;
   bool inflight = false;  // device-variant steps have been enqueued since the last synchronisation
   // staging for the host variant
   PinnedBuf<float> h_in, h_out;
@@ -936,6 +946,10 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
     for (int blk = 0; blk < B_NBLOCKS; ++blk) b->row_slot[blk].assign((size_t)B * H, 0);
     for (int s = 0; s < B; ++s) { sync_stream_arrays(b, s); fill_row_slots(b, s); }
     for (int blk = 0; blk < B_NBLOCKS; ++blk) rebuild_tiles(b, blk);
+    std::vector<sblob::RingShape> shapes;
+    for (const RingArena* a : {&b->phone.arena, &b->pitch.arena, &b->wave.arena})
+      for (const Ring* r : a->rings) shapes.push_back(sblob::RingShape{r->C, r->n, r->m});
+    b->sb.layout = sblob::make_layout(H, shapes.data(), (int)shapes.size(), (uint32_t)sizeof(StreamCfg), (uint32_t)sizeof(Wrap48State));
   }
   return b;
 }
@@ -1408,6 +1422,159 @@ int BeatriceBatch_ResetStreamInFlight(BeatriceBatch* b, int stream) {
   return BeatriceBatch_FlushSpeaker(b, stream);
 }
 long long BeatriceBatch_TicksLaunched(const BeatriceBatch* b) { return b && b->tk.on ? b->tk.tick : 0; }
+
+// ---- a stream's state from one batch into another (beatrice_batch.h; the blob: stream_blob.h, the kernels: stream_blob.hip) -----------
+// What travels is what BeatriceBatch_ResetStream clears -- the stream's part of the three arenas, the pitch head's previous bin, its
+// Wrap48State -- plus its StreamCfg and its lottery engine.  Both calls work at a drained point (sync_all: every stream stands at the
+// batch's one counter, tick_relevel has run), so a blob is "the stream before step `counter`", and the destination, which stands at a
+// counter of its own, turns every ring by the difference as it takes the blob in.
+namespace {
+bool blob_streams_ok(const BeatriceBatch* b, int n, const int* streams) {
+  if (n < 1 || n > b->B || !streams) return false;
+  std::vector<char> seen(b->B, 0);
+  for (int i = 0; i < n; ++i) {
+    if (streams[i] < 0 || streams[i] >= b->B || seen[streams[i]]) return false;
+    seen[streams[i]] = 1;
+  }
+  return true;
+}
+// the piece table (once per batch, the way tick_reset_prepare builds its ring table) and staging for min(n, 16) blobs
+bool blob_prepare(BeatriceBatch* b, int n) {
+  BeatriceBatch::StreamBlobs& sb = b->sb;
+  const sblob::Layout& l = sb.layout;
+  if (!sb.d_pieces) {
+    std::vector<BlobPiece> pieces;
+    for (const RingArena* a : {&b->phone.arena, &b->pitch.arena, &b->wave.arena})
+      for (const Ring* r : a->rings) pieces.push_back(BlobPiece{r->base, (unsigned)ring_stream_floats(*r), (unsigned)(r->n * r->C), r->m, 0});
+    pieces.push_back(BlobPiece{reinterpret_cast<float*>(b->pitch.d_prev_q), 1u, 1u, 1, 0});   // (an int: copied as a word)
+    const unsigned w48 = (unsigned)(sizeof(Wrap48State) / sizeof(float));
+    pieces.push_back(BlobPiece{reinterpret_cast<float*>(b->d_w48.get()), w48, w48, 1, 0});
+    if (pieces.size() != l.pieces.size()) return false;
+    for (size_t i = 0; i < pieces.size(); ++i) {
+      if (pieces[i].slot_floats != l.pieces[i].slot_floats || pieces[i].m != l.pieces[i].m) return false;
+      pieces[i].blob_off = l.pieces[i].off;
+    }
+    DevBuf<BlobPiece> d_pieces;
+    if (!d_pieces.alloc(pieces.size(), "blob piece table", false) ||
+        !hip_ok(hipMemcpy(d_pieces, pieces.data(), sizeof(BlobPiece) * pieces.size(), hipMemcpyHostToDevice), "blob piece table up"))
+      return false;
+    sb.n_pieces = (int)pieces.size(); sb.d_pieces = std::move(d_pieces);
+  }
+  const int want = std::min(n, sblob::kMaxRound);
+  if (sb.cap < want) {
+    PinnedBuf<unsigned char> h_stage;
+    DevBuf<unsigned char> d_stage;
+    if (!h_stage.alloc((size_t)want * l.blob_bytes, "blob staging", false) || !d_stage.alloc((size_t)want * l.blob_bytes, "blob staging")) return false;
+    sb.h_stage = std::move(h_stage); sb.d_stage = std::move(d_stage); sb.cap = want;
+  }
+  return true;
+}
+void blob_indices_of(const StreamCfg& c, int32_t* idx) {
+  idx[0] = c.target_speaker; idx[1] = c.additive_speaker; idx[2] = c.codebook_speaker;
+  for (int i = 0; i < B_NBLOCKS; ++i) idx[3 + i] = c.kv_slot[i];
+  for (int i = 0; i < 8; ++i) idx[3 + B_NBLOCKS + i] = c.codebook_row[i];
+}
+void blob_indices_into(StreamCfg& c, const int32_t* idx) {
+  c.target_speaker = idx[0]; c.additive_speaker = idx[1]; c.codebook_speaker = idx[2];
+  for (int i = 0; i < B_NBLOCKS; ++i) c.kv_slot[i] = idx[3 + i];
+  for (int i = 0; i < 8; ++i) c.codebook_row[i] = idx[3 + B_NBLOCKS + i];
+}
+// the settings of a blob hold what the setters can have put there (the table indices are checked apart: sblob::map_indices)
+bool blob_cfg_ok(const StreamCfg& c) {
+  return c.kv_set_count >= 0 && c.kv_set_count <= B_NBLOCKS && c.kv_delay >= 0 && c.kv_delay <= 4 && c.formant_index >= 0 && c.formant_index <= 8 &&
+         c.vq_k >= 0 && c.vq_k <= 8 && c.min_q >= 1 && c.min_q < B_PITCH_BINS && c.max_q >= 1 && c.max_q < B_PITCH_BINS &&
+         c.pitch.pitch_correction_type >= 0 && c.pitch.pitch_correction_type <= 1;
+}
+static_assert(sblob::kIndices == 3 + B_NBLOCKS + 8 && std::is_trivially_copyable<StreamCfg>::value && sizeof(Wrap48State) % sizeof(float) == 0, "blob settings");
+}  // namespace
+
+size_t BeatriceBatch_StreamBlobBytes(const BeatriceBatch* b) { return b && b->ok ? b->sb.layout.blob_bytes : 0; }
+
+int BeatriceBatch_ExportStreams(BeatriceBatch* b, int n, const int* streams, void* blobs) {
+  BATCH_OPEN(b);
+  if (!blob_streams_ok(b, n, streams) || !blobs) return -1;
+  // a reset that waits for the stream's next step has not happened yet: the rings still hold what it is to clear
+  if (b->tk.on && b->tk.any_reset_pending && (int)b->tk.reset_pending.size() == b->B)
+    for (int i = 0; i < n; ++i) if (b->tk.reset_pending[streams[i]]) return -3;
+  if (!blob_prepare(b, n) || !sync_all(b)) return -2;
+  BeatriceBatch::StreamBlobs& sb = b->sb;
+  const sblob::Layout& l = sb.layout;
+  unsigned char* out = static_cast<unsigned char*>(blobs);
+  for (int at = 0; at < n; at += sb.cap) {
+    BlobRound round{};
+    round.n = std::min(sb.cap, n - at);
+    for (int j = 0; j < round.n; ++j) round.streams[j] = streams[at + j];
+    if (!stream_gather(sb.d_pieces, sb.n_pieces, round, reinterpret_cast<float*>(sb.d_stage.get()), l.blob_bytes / sizeof(float), b->stream) ||
+        !hip_ok(hipMemcpyAsync(sb.h_stage, sb.d_stage, (size_t)round.n * l.blob_bytes, hipMemcpyDeviceToHost, b->stream), "blobs down") ||
+        !hip_ok(hipStreamSynchronize(b->stream), "stream gather"))
+      return -2;
+    for (int j = 0; j < round.n; ++j) {
+      unsigned char* blob = sb.h_stage + (size_t)j * l.blob_bytes;
+      const StreamCfg& c = b->cfg[round.streams[j]];
+      int32_t idx[sblob::kIndices];
+      blob_indices_of(c, idx);
+      std::memset(blob, 0, l.off_state);
+      sblob::write_header(l, b->hop_host, blob);
+      std::memcpy(blob + l.off_indices, idx, sizeof(idx));
+      std::memcpy(blob + l.off_cfg, &c, sizeof(c));
+      if (!sblob::engine_out(b->lottery[round.streams[j]], blob + l.off_engine)) return -2;
+      std::memcpy(out + (size_t)(at + j) * l.blob_bytes, blob, l.blob_bytes);
+    }
+  }
+  return 0;
+}
+
+int BeatriceBatch_ImportStreams(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
+  BATCH_OPEN(b);
+  if (!blob_streams_ok(b, n, streams) || !blobs || n_map < 0 || (entry_map == nullptr) != (n_map == 0)) return -1;
+  BeatriceBatch::StreamBlobs& sb = b->sb;
+  const sblob::Layout& l = sb.layout;
+  const unsigned char* in = static_cast<const unsigned char*>(blobs);
+  struct Taken { StreamCfg cfg; std::mt19937 engine; int counter; };
+  std::vector<Taken> taken(n);
+  for (int i = 0; i < n; ++i) {   // every blob is looked at before anything is drained, uploaded or written
+    const unsigned char* blob = in + (size_t)i * l.blob_bytes;
+    int32_t idx[sblob::kIndices];
+    if (sblob::validate_header(l, blob, l.blob_bytes, B_HOP_WRAP, &taken[i].counter) != sblob::kOk ||
+        sblob::map_indices(l, blob, entry_map, n_map, b->n_speakers, b->max_speakers, idx) != sblob::kOk)
+      return -1;
+    std::memcpy(&taken[i].cfg, blob + l.off_cfg, sizeof(StreamCfg));
+    if (!blob_cfg_ok(taken[i].cfg) || !sblob::engine_in(blob + l.off_engine, &taken[i].engine)) return -1;
+    blob_indices_into(taken[i].cfg, idx);
+  }
+  if (!blob_prepare(b, n) || !sync_all(b)) return -2;
+  for (int at = 0; at < n; at += sb.cap) {
+    BlobRound round{};
+    round.n = std::min(sb.cap, n - at);
+    for (int j = 0; j < round.n; ++j) {
+      round.streams[j] = streams[at + j];
+      round.shift[j] = sblob::counter_shift(b->hop_host, taken[at + j].counter, B_HOP_WRAP);
+    }
+    std::memcpy(sb.h_stage, in + (size_t)at * l.blob_bytes, (size_t)round.n * l.blob_bytes);
+    if (!hip_ok(hipMemcpyAsync(sb.d_stage, sb.h_stage, (size_t)round.n * l.blob_bytes, hipMemcpyHostToDevice, b->stream), "blobs up") ||
+        !stream_scatter(sb.d_pieces, sb.n_pieces, round, reinterpret_cast<const float*>(sb.d_stage.get()), l.blob_bytes / sizeof(float), b->stream) ||
+        !hip_ok(hipStreamSynchronize(b->stream), "stream scatter"))
+      return -2;
+  }
+  // the settings, as a change of every setting of the stream at once: the existing path takes them to the device with the next step
+  for (int i = 0; i < n; ++i) {
+    const int s = streams[i];
+    b->cfg[s] = taken[i].cfg;
+    b->lottery[s] = taken[i].engine;
+    sync_stream_arrays(b, s);   // (recount, the front part of the settings block)
+    fill_row_slots(b, s);       // (a pending install moves them block by block from the next step on: advance_kv)
+    if ((int)b->tk.reset_pending.size() == b->B) b->tk.reset_pending[s] = 0;   // a reset still waiting for this slot's next step: the blob replaces what it would clear
+  }
+  if (b->tk.any_reset_pending) {
+    b->tk.any_reset_pending = false;
+    for (const unsigned char p : b->tk.reset_pending) b->tk.any_reset_pending = b->tk.any_reset_pending || p != 0;
+  }
+  b->pending_kv = 0;
+  for (const StreamCfg& c : b->cfg) if (c.kv_set_count < B_NBLOCKS) ++b->pending_kv;
+  b->vq_dirty = true;
+  for (int blk = 0; blk < B_NBLOCKS; ++blk) rebuild_tiles(b, blk);   // (marks every copy of the wave part for upload)
+  return 0;
+}
 
 // ---- per-hop ------------------------------------------------------------------------------------
 int BeatriceBatch_ConvertFramesDevice(BeatriceBatch* b, const float* d_in, float* d_out) {

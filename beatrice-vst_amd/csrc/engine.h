@@ -322,4 +322,14 @@ constexpr size_t kInstallEntryFloats = (size_t)B_CODEBOOK * B_PHONE_CH + B_HID +
 bool install_entries(const MorphDesc* descs, const float* staged, int n, int n_entries, float* d_cb_raw, float* d_add_raw, float* d_kv_raw,
                      float* d_cbT, float* d_cnorm, hipStream_t stream);
 
+// A stream's device state between the batch and blobs in a staging buffer (BeatriceBatch_ExportStreams / ImportStreams; stream_blob.hip,
+// the blob's format: stream_blob.h).  A piece = one ring of the three arenas, the pitch head's previous bin or the 48 kHz wrapper's
+// history: stream s's part is m slots of slot_floats words at base + s * stride, and sits at word blob_off of a blob.  A round = up to
+// 16 blobs, one launch: blob j of the staging buffer (blob_floats words each) is stream streams[j]; on the way in a piece with m > 1
+// turns by shift[j] % m slots (slot i of the blob lands in slot (i + shift[j]) % m).
+struct BlobPiece { float* base; unsigned stride, slot_floats; int m; unsigned long long blob_off; };
+struct BlobRound { int n; int streams[16]; int shift[16]; };
+bool stream_gather(const BlobPiece* d_pieces, int n_pieces, const BlobRound& round, float* d_staging, size_t blob_floats, hipStream_t stream);
+bool stream_scatter(const BlobPiece* d_pieces, int n_pieces, const BlobRound& round, const float* d_staging, size_t blob_floats, hipStream_t stream);
+
 }  // namespace bhip

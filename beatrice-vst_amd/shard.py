@@ -186,6 +186,27 @@ def affine_speaker(rank, world, local_stream, n_speakers):
     return rank + world * (local_stream % mine)
 
 
+def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None, reset_source=False):
+    """Stream src_streams[i] of src_batch goes on as stream dst_streams[i] of dst_batch, with its state and settings
+    (Batch.export_streams / Batch.import_streams): its next step there is bit for bit the step it would have run in
+    src_batch.  Both batches drain.  The two are batches of ONE process (any two GPUs of it: each call runs on its batch's
+    device); they must come from the same library build and have the same hops per step.  entry_map[i] = the table entry of
+    dst_batch that holds what entry i of src_batch holds (None: the same entries) -- that the tables, and an active morph's
+    weights, are equal there is the caller's promise.  reset_source: BeatriceBatch_ResetStream on the source streams
+    afterwards, so that the slots start from silence for their next users.  Returns the blobs.
+
+    Between ranks the blob is plain bytes: export_streams on the rank that has the stream, broadcast_bytes (or a
+    point-to-point send of a uint8 tensor) to the rank that takes it, import_streams there."""
+    if len(src_streams) != len(dst_streams):
+        raise ValueError("move_streams: %d source streams, %d destination streams" % (len(src_streams), len(dst_streams)))
+    blobs = src_batch.export_streams(src_streams)
+    dst_batch.import_streams(dst_streams, blobs, entry_map)
+    if reset_source:
+        for s in src_streams:
+            src_batch._check(src_batch.a.BeatriceBatch_ResetStream(src_batch.h, int(s)))
+    return blobs
+
+
 def max_over_ranks(value, world, dist, torch, device):
     if world == 1:
         return value

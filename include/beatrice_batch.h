@@ -315,6 +315,39 @@ int BeatriceBatch_ResetStreamInFlight(BeatriceBatch* b, int stream);
 /* Tick launches since tick mode was entered (fill and drain ticks included); 0 outside tick mode. */
 long long BeatriceBatch_TicksLaunched(const BeatriceBatch* b);
 
+/* A stream moves from one batch into another WITH its state (a larger batch when load rises, the batch on the GPU that holds its voice,
+ * the last live streams of a nearly idle batch): after BeatriceBatch_ExportStreams(X, s) and BeatriceBatch_ImportStreams(Y, t), the next
+ * step of stream t of Y is bit for bit the step stream s of X would have run next on the same input, and so is every step after it.  X
+ * is not changed by the export; no other stream of Y is changed by the import.
+ * A blob holds exactly what BeatriceBatch_ResetStream clears, plus the stream's settings.  State: the stream's part of every activation
+ * ring of the three modules, the pitch head's previous bin, the 48 kHz wrapper's history (BeatriceBatch_ConvertBlocks48k*,
+ * BeatriceBatch_BindResidentIO48k).  Settings: target, additive and codebook speaker, the installed key/value entries and how many of a
+ * pending switch are still to come (they go on installing one per hop in the destination), formant shift, VQ neighbours, pitch range and
+ * pitch parameters, and the stream's codebook-lottery engine, which continues its sequence.  A header names the hops per step, the source
+ * batch's step counter and the layout of every ring.  NOT in a blob, because it belongs to the slot and BeatriceBatch_ResetStream does
+ * not restart it either: the any-rate wrapper's per-stream state (BeatriceBatch_ProcessBlocks*, BeatriceBatch_BindResidentBlocks*: the
+ * resampler histories, the 480-sample FIFO, the gain clocks, the per-stream rate clocks).
+ * A blob is a short-lived token between two batches of the SAME library build with the same hops per step, not a storage format:
+ * BeatriceBatch_ImportStreams refuses whatever it does not recognise and attempts no compatibility.  Between processes it is plain bytes.
+ * Both calls work in every mode and are settings, not mode entry points (no row in the MODES table).  Both drain as
+ * BeatriceBatch_ResetStream does, after which every stream stands at the batch's one step counter.  Export then gathers the n streams in
+ * one launch per 16 streams and waits.  Import validates EVERY blob first, then uploads and scatters in one launch per 16 streams: every
+ * ring with more than one step slot is turned by (destination counter - source counter) mod its slot count on the way in.  It replaces
+ * the destination streams' settings and lottery engines -- the next step takes them to the device like any other changed setting -- and
+ * cancels a BeatriceBatch_ResetStreamInFlight still waiting on a destination stream.
+ * entry_map: every speaker-table index of a blob goes through it (index i becomes entry_map[i]), so the destination may hold the same
+ * voices at other entries; NULL, 0 keeps the indices.  That the entries named hold the same tables as in the source -- for a morph entry
+ * the same active morph with the same weights -- is the caller's promise; nothing checks it.
+ * All or nothing.  -1 and no change (no drain, no launch, nothing staged): n < 1 or n > the batch's streams; a NULL pointer (entry_map
+ * NULL with n_map != 0 included); a stream out of range or named twice; on import a blob with a bad magic word, version or size, other
+ * hops per step than the batch's, a ring layout that does not match, settings out of their ranges, an index outside entry_map (without
+ * a map: outside the table's capacity), or a mapped index outside [0, n_speakers) of the destination.  -3 and no change: export of a
+ * stream with a BeatriceBatch_ResetStreamInFlight pending that no step has taken yet.  -2: HIP or allocation failure. */
+size_t BeatriceBatch_StreamBlobBytes(const BeatriceBatch* b);   /* bytes of ONE stream's blob; the same for every stream of b */
+int BeatriceBatch_ExportStreams(BeatriceBatch* b, int n, const int* streams, void* blobs /* host, n * StreamBlobBytes(b) */);
+int BeatriceBatch_ImportStreams(BeatriceBatch* b, int n, const int* streams, const void* blobs /* host, n blobs */,
+                                const int* entry_map, int n_map /* NULL, 0: speaker-table indices are kept as they are */);
+
 /* One step (H hops, H = 1 unless created with BeatriceBatch_CreateBlock) for every stream.
  * Host variant: in [B][H*160] @16 kHz, out [B][H*240] @24 kHz, synchronous.
  * Device variant: pointers are device memory, work is enqueued on the batch's HIP stream and the
