@@ -24,11 +24,15 @@ struct Ring {
 // emits global_load / global_store with their own counter and the ISA shows the intended `s_waitcnt vmcnt(8) lgkmcnt(7)`).
 // MEASURED (round 4, same box, A/B) for EVERY pointer of EVERY body (globalize() below, -DFUSE_GLOBALIZE): the tick launch is
 // 4 % SLOWER with it (69.2 vs 66.5 us at 256 streams, 241 vs 232 us at 1 024) -- VGPR spills 48 -> 112 in the table kernel.
-// That switch stays off.  The NARROW form is on: only the weight stream and the row gather of the GEMM bodies' segment loops
-// (rowchain.hip.h rc::WGlobal, load_tile, conv_rows_body's load_seg) go through as_global, inside the bodies themselves.  Their
-// bases are wave-uniform, so the loads are global_load off a SCALAR base with a 32-bit lane offset: no VGPR pair per column
-// tile, the base advanced by scalar adds, a counted vmcnt wait per k-block, and LDS waits that leave the prefetch in flight.
-// Same-box A/B at 256 streams x 4 hops: 234.6 -> 224.4 us per tick launch, spills 241 -> 231 (profiles/weight_stream_notes.md).
+// That switch stays off.  The NARROW form is on, inside the bodies themselves and with FEWER registers, not more: a wave-uniform
+// base made global in SCALAR registers plus one 32-bit lane offset (WGlobal / GBase below): no VGPR pair per address, the base
+// advanced by scalar adds, counted vmcnt waits, and LDS waits that leave the prefetch in flight.  First the weight stream and the
+// row gather of the GEMM bodies' segment loops (rowchain.hip.h WGlobal, load_tile, conv_rows_body's load_seg): same-box A/B at
+// 256 streams x 4 hops 234.6 -> 224.4 us per tick launch, spills 241 -> 231 (profiles/weight_stream_notes.md).  Then the tail stages
+// (tail_stages.hip.h, TST_GLOBAL: weights, ring frames, state block, samples): 223.8 -> 214.8 us, fewer spills again
+// (profiles/flat_to_global_tail_notes.md).  Measured beside it and NOT kept, because their gain stayed inside five spreads
+// (tools/experiments/r09_gru_epi_quad_global.patch): the same form for the GRU cells, the epilogues and the quad body's K / V rows.
+// Still generic, then: those, the per-stream bodies of wave_tail.hip.h and kernels_misc.hip.h, attn_pv_body, the linked cells' granules.
 // (A plain generic -> global -> generic cast is folded away by the front end; the empty asm between the two casts keeps it.
 //  "s": the pointer is wave-uniform and stays in scalar registers -- as_global_v for a pointer that may differ between lanes.)
 template <class T>
@@ -46,6 +50,67 @@ __device__ __forceinline__ T* as_global_v(T* p) {
   asm("" : "+v"(g));
   return (T*)g;
 }
+// A wave-uniform GLOBAL base in scalar registers; the lane's part of an address is one unsigned 32-bit BYTE offset and a compile-time
+// distance.  Loads and stores through it are `global_load / global_store v, v_off, s[base:base+1] offset:imm`: no 64-bit VGPR pair
+// and no v_add_co / v_addc per address, and the access counts on vmcnt alone.  The offset is UNSIGNED: a caller whose lane part may
+// be negative before the compile-time distance is added moves the base down instead (of()'s `bytes`), so that the lane part is >= 0.
+struct GBase {
+  typedef __attribute__((address_space(1))) char gbyte;
+  typedef float gf4 __attribute__((ext_vector_type(4)));
+  gbyte* p;
+  template <class T>
+  __device__ static __forceinline__ GBase of(const T* uniform, const long long bytes = 0) {
+    return GBase{(gbyte*)as_global(reinterpret_cast<char*>(reinterpret_cast<unsigned long long>(uniform) + (unsigned long long)bytes))};
+  }
+  __device__ __forceinline__ float ldf(const unsigned voff, const int imm = 0) const {
+    return *reinterpret_cast<const __attribute__((address_space(1))) float*>(p + (size_t)voff + imm);
+  }
+  __device__ __forceinline__ float4 ld4(const unsigned voff, const int imm = 0) const {
+    const gf4 v = *reinterpret_cast<const __attribute__((address_space(1))) gf4*>(p + (size_t)voff + imm);
+    return make_float4(v[0], v[1], v[2], v[3]);
+  }
+  __device__ __forceinline__ void stf(const unsigned voff, const int imm, const float v) const {
+    *reinterpret_cast<__attribute__((address_space(1))) float*>(p + (size_t)voff + imm) = v;
+  }
+  __device__ __forceinline__ void st4(const unsigned voff, const int imm, const float4 v) const {
+    *reinterpret_cast<__attribute__((address_space(1))) gf4*>(p + (size_t)voff + imm) = gf4{v.x, v.y, v.z, v.w};
+  }
+};
+// The same interface over a GENERIC pointer (flat accesses wherever the pointer came from a table in device memory): what the tail
+// stages' A/B switch (-DTST_GLOBAL=0) builds with.
+struct FBase {
+  char* p;
+  template <class T>
+  __device__ static __forceinline__ FBase of(const T* uniform, const long long bytes = 0) {
+    return FBase{reinterpret_cast<char*>(reinterpret_cast<unsigned long long>(uniform) + (unsigned long long)bytes)};
+  }
+  __device__ __forceinline__ float ldf(const unsigned voff, const int imm = 0) const { return *reinterpret_cast<const float*>(p + (size_t)voff + imm); }
+  __device__ __forceinline__ float4 ld4(const unsigned voff, const int imm = 0) const { return *reinterpret_cast<const float4*>(p + (size_t)voff + imm); }
+  __device__ __forceinline__ void stf(const unsigned voff, const int imm, const float v) const { *reinterpret_cast<float*>(p + (size_t)voff + imm) = v; }
+  __device__ __forceinline__ void st4(const unsigned voff, const int imm, const float4 v) const { *reinterpret_cast<float4*>(p + (size_t)voff + imm) = v; }
+};
+// Where a wavefront's packed weight fragments come from: the record of k-block kb is 64 float4, lane l's at `u + kb * 64 + l`.  `u` is
+// WAVE-UNIFORM (layer, column tile), so the base is a global pointer in scalar registers and the lane's part one 32-bit byte offset
+// shared by every column tile (rowchain.hip.h: the segment loops; tail_stages.hip.h fetch_b).
+struct WGlobal {
+  typedef __attribute__((address_space(1))) const char gbyte;
+  typedef float gf4 __attribute__((ext_vector_type(4)));
+  gbyte* base;     // wave-uniform, scalar registers
+  unsigned voff;   // lane x 16
+  __device__ static __forceinline__ WGlobal make(const float4* u, const int lane) {
+    return WGlobal{(gbyte*)reinterpret_cast<const char*>(as_global(u)), (unsigned)lane * 16u};
+  }
+  __device__ __forceinline__ WGlobal at(const size_t f4) const { return WGlobal{base + f4 * 16, voff}; }
+  // Eight k-blocks (8 KiB) share one scalar base: the load's 13-bit signed immediate reaches -4096 .. +3072 around it.  The empty
+  // asm keeps that base a scalar value of its own -- left to itself the compiler folds "base + lane offset" into ONE 64-bit VGPR
+  // pair and advances THAT with a v_add_co / v_addc pair per column tile and four k-blocks, which is what this form removes.
+  __device__ __forceinline__ float4 kblock(const int kb) const {
+    gbyte* q = base + ((size_t)(kb & ~7) * 1024 + 4096);
+    asm("" : "+s"(q));
+    const gf4 v = *reinterpret_cast<__attribute__((address_space(1))) const gf4*>(q + (size_t)voff + ((kb & 7) * 1024 - 4096));
+    return make_float4(v[0], v[1], v[2], v[3]);
+  }
+};
 // globalize(args): every pointer of an argument block through as_global (one overload per block type, next to its struct)
 __device__ __forceinline__ void globalize(Ring& r) { r.base = as_global(r.base); }
 
@@ -65,6 +130,12 @@ __device__ __forceinline__ unsigned ring_index(const Ring& r, int b, int pos, in
   return (unsigned)(b * R + f) * (unsigned)r.C;
 }
 __device__ __forceinline__ float* ring_frame(const Ring& r, int b, int pos, int rel) { return r.base + ring_index(r, b, pos, rel); }
+// The same through a scalar base (GBase / FBase above): the ring at stream b0 -- a workgroup's first -- and the byte offset of frame
+// (pos + rel), channel c of the workgroup's stream s from there.  A workgroup holds a few dozen streams at most, so the offset fits
+// 32 bits whatever the ring's size.
+template <class Base>
+__device__ __forceinline__ Base ring_at(const Ring& r, const int b0) { return Base::of(r.base, (long long)b0 * (long long)ring_stream_floats(r) * 4); }
+__device__ __forceinline__ unsigned ring_off(const Ring& r, const int s, const int pos, const int rel, const int c) { return (ring_index(r, s, pos, rel) + (unsigned)c) * 4u; }
 
 // The step counter a kernel works on, and the slot of resident I/O buffers that belongs to it.  Ordinary launches read
 // the pair from device memory (args.hop); in the batch's tick launch (tick.hip.h) the table kernel takes every stage's

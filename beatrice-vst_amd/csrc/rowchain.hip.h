@@ -135,24 +135,7 @@ struct WLane {
   __device__ __forceinline__ WLane at(const size_t f4) const { return WLane{p + f4}; }   // f4: a uniform distance in float4
   __device__ __forceinline__ float4 kblock(const int kb) const { return p[(size_t)kb * 64]; }
 };
-struct WGlobal {
-  typedef __attribute__((address_space(1))) const char gbyte;
-  gbyte* base;     // wave-uniform, scalar registers
-  unsigned voff;   // lane x 16
-  __device__ static __forceinline__ WGlobal make(const float4* u, const int lane) {
-    return WGlobal{(gbyte*)reinterpret_cast<const char*>(as_global(u)), (unsigned)lane * 16u};
-  }
-  __device__ __forceinline__ WGlobal at(const size_t f4) const { return WGlobal{base + f4 * 16, voff}; }
-  // Eight k-blocks (8 KiB) share one scalar base: the load's 13-bit signed immediate reaches -4096 .. +3072 around it.  The empty
-  // asm keeps that base a scalar value of its own -- left to itself the compiler folds "base + lane offset" into ONE 64-bit VGPR
-  // pair and advances THAT with a v_add_co / v_addc pair per column tile and four k-blocks, which is what this form removes.
-  __device__ __forceinline__ float4 kblock(const int kb) const {
-    gbyte* q = base + ((size_t)(kb & ~7) * 1024 + 4096);
-    asm("" : "+s"(q));
-    const f32x4 v = *reinterpret_cast<__attribute__((address_space(1))) const f32x4*>(q + (size_t)voff + ((kb & 7) * 1024 - 4096));
-    return make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
+using ::WGlobal;   // (ring.h: shared with the tail stages)
 #if RC_WSTREAM_GLOBAL
 using WStream = WGlobal;
 #else

@@ -71,6 +71,28 @@ __device__ __forceinline__ void globalize(StageArgs& a) {
   a.fin_w = as_global(a.fin_w); a.fin_b = as_global(a.fin_b); a.d_out = as_global(a.d_out); a.hop = as_global(a.hop);
 }
 
+// How the stages reach global memory.  Their argument block comes from the tick launch's table in device memory, so its pointers are
+// generic to the compiler and every access through them was a flat one, counting on the LDS counter too: the lgkmcnt wait in front
+// of pass()'s first A operands drained the NEXT layer's weight prefetch and the residual loads that had been issued to hide behind
+// the MFMAs, and every state or ring store held up the next LDS wait (ring.h, profiles/flat_to_global_tail_notes.md).  TST_GLOBAL = 1:
+// every pointer is made global once per body, and the accesses of the hot paths take the form of ring.h's GBase / WGlobal -- a
+// SCALAR base per workgroup (the ring, the state block, the output at the workgroup's first stream) plus the lane's unsigned 32-bit
+// byte offset, which inside a workgroup's few streams is small by construction.  -DTST_GLOBAL=0: the same addressing over generic
+// pointers (flat accesses), for A/B builds.
+#ifndef TST_GLOBAL
+#define TST_GLOBAL 1
+#endif
+#if TST_GLOBAL
+using TBase = GBase;
+#else
+using TBase = FBase;
+#endif
+// the workgroup's bases: a ring / the state block at its first stream b0 (`floats`: a distance added to the base, may be negative)
+__device__ __forceinline__ TBase ring_wg(const Ring& r, const int b0) { return ring_at<TBase>(r, b0); }
+__device__ __forceinline__ TBase state_wg(const StageArgs& a, const int b0, const int floats = 0) {
+  return TBase::of(a.state, ((long long)b0 * TAIL_STATE_FLOATS + floats) * 4);
+}
+
 // lrelu(x) = max(x, 0.1 x), bit for bit MODEL_SPEC's `x > 0 ? x : 0.1 x` (x and 0.1 x have the same sign).  The instruction
 // itself: fmaxf() makes the compiler canonicalise both operands first (two more VALU instructions per value).
 __device__ __forceinline__ float lrelu_max(float x) {
@@ -107,6 +129,17 @@ struct Split {
 template <int K, int NOUT, int KB0 = 0, int KB1 = K / 16>
 __device__ __forceinline__ void fetch_b(const float* __restrict__ wpacked, float4 (&bf)[Split<NOUT>::CT][K / 16], int wave, int lane) {
   using SP = Split<NOUT>;
+#if TST_GLOBAL
+  // (the column tile is wave-uniform: the fragments' base stays in scalar registers, the lane's part is lane x 16 bytes)
+  const int wn = __builtin_amdgcn_readfirstlane(wave) % SP::NWN;
+  const WGlobal w0 = WGlobal::make(reinterpret_cast<const float4*>(wpacked), lane);
+#pragma unroll
+  for (int ct = 0; ct < SP::CT; ++ct) {
+    const WGlobal w = w0.at((size_t)(SP::POW2 ? wn : ct) * (K / 16) * 64);
+#pragma unroll
+    for (int kb = KB0; kb < KB1; ++kb) bf[ct][kb] = w.kblock(kb);
+  }
+#else
   const int wn = wave % SP::NWN;
 #pragma unroll
   for (int ct = 0; ct < SP::CT; ++ct) {
@@ -115,6 +148,7 @@ __device__ __forceinline__ void fetch_b(const float* __restrict__ wpacked, float
 #pragma unroll
     for (int kb = KB0; kb < KB1; ++kb) bf[ct][kb] = p[(size_t)kb * 64];
   }
+#endif
 }
 
 #ifndef TST_PIN
@@ -268,11 +302,10 @@ __device__ __forceinline__ bool live_s(const int* shop, const int b0, const int 
   else return b0 + s < B;
 }
 template <int S, int N, bool RAG>
-__device__ __forceinline__ float4 state_load(const float* __restrict__ state, const int ts_off, const int b0, const int* shop, const int B, const int tid) {
+__device__ __forceinline__ float4 state_load(const TBase gst /* state_wg(a, b0) */, const int ts_off, const int b0, const int* shop, const int B, const int tid) {
   static_assert(N % 4 == 0 && S * N / 4 <= NTHR, "one float4 per thread");
   const int s = tid / (N / 4), q = tid % (N / 4);
-  return tid < S * N / 4 && live_s<RAG>(shop, b0, s, B) ? *reinterpret_cast<const float4*>(state + (size_t)(b0 + s) * TAIL_STATE_FLOATS + ts_off + 4 * q)
-                                         : make_float4(0.f, 0.f, 0.f, 0.f);
+  return tid < S * N / 4 && live_s<RAG>(shop, b0, s, B) ? gst.ld4((unsigned)(s * TAIL_STATE_FLOATS + ts_off + 4 * q) * 4u) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 // the streams of a workgroup: their step counters (the common one; their own in a ragged tick step; -1 where there is no stream)
 template <int S, bool RAG>
@@ -308,21 +341,22 @@ __device__ __forceinline__ void prologue(const StageArgs& a, const int hop, cons
                                          float* __restrict__ hc, const int tid, const int* shop, const int fb = 0, const bool first = true, const bool last = true) {
   constexpr int F4 = C / 4, ROWS = T + 2, N = S * ROWS * F4, NIT = (N + NTHR - 1) / NTHR;
   const int pos = ring_pos(a.in, hop);
+  const TBase gin = ring_wg(a.in, b0), gst = state_wg(a, b0);
   float4 v[NIT];
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int e = tid + it * NTHR;
-    const int s = e / (ROWS * F4), q = e % (ROWS * F4), t = q / F4 - 2, c4 = q % F4, b = b0 + s;
+    const int s = e / (ROWS * F4), q = e % (ROWS * F4), t = q / F4 - 2, c4 = q % F4;
     v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (e < N && live_s<RAG>(shop, b0, s, a.B)) {
-      if (IN_FROM_RING_HISTORY || t + fb >= 0) v[it] = *reinterpret_cast<const float4*>(ring_frame(a.in, b, stream_pos<RAG>(a.in, pos, shop, s), t + fb) + 4 * c4);
-      else v[it] = *reinterpret_cast<const float4*>(a.state + (size_t)b * TAIL_STATE_FLOATS + TS_IN + (t + 2) * C + 4 * c4);
+      if (IN_FROM_RING_HISTORY || t + fb >= 0) v[it] = gin.ld4(ring_off(a.in, s, stream_pos<RAG>(a.in, pos, shop, s), t + fb, 4 * c4));
+      else v[it] = gst.ld4((unsigned)(s * TAIL_STATE_FLOATS + TS_IN + (t + 2) * C + 4 * c4) * 4u);
     }
   }
   float4 hb = make_float4(0.f, 0.f, 0.f, 0.f), hcv = hb;
   if (first) {
-    hb = state_load<S, 6 * C, RAG>(a.state, TS_B, b0, shop, a.B, tid);
-    hcv = state_load<S, HC_ROWS * C, RAG>(a.state, TS_C, b0, shop, a.B, tid);
+    hb = state_load<S, 6 * C, RAG>(gst, TS_B, b0, shop, a.B, tid);
+    hcv = state_load<S, HC_ROWS * C, RAG>(gst, TS_C, b0, shop, a.B, tid);
   }
   // ---- every load above is in flight; now the stores
 #pragma unroll
@@ -371,9 +405,10 @@ __device__ __forceinline__ void stash_to_rows(float* __restrict__ buf, const flo
 }
 template <int C, int S, int TS_IN, bool RAG>
 __device__ __forceinline__ void hin_to_state(const StageArgs& a, const float* __restrict__ hin, const int b0, const int tid, const int* shop) {
+  const TBase gst = state_wg(a, b0);
   for (int e = tid; e < S * 2 * C / 4; e += NTHR) {
     const int s = e / (2 * C / 4), q = e % (2 * C / 4);
-    if (live_s<RAG>(shop, b0, s, a.B)) *reinterpret_cast<float4*>(a.state + (size_t)(b0 + s) * TAIL_STATE_FLOATS + TS_IN + 4 * q) = *reinterpret_cast<const float4*>(hin + 4 * e);
+    if (live_s<RAG>(shop, b0, s, a.B)) gst.st4((unsigned)(s * TAIL_STATE_FLOATS + TS_IN + 4 * q) * 4u, 0, *reinterpret_cast<const float4*>(hin + 4 * e));
   }
 }
 
@@ -392,27 +427,30 @@ __device__ __forceinline__ void two_res_layers(const StageArgs& a, const int hop
   static_assert(Split<C>::CT == 1, "one column tile per wavefront");
   constexpr bool IN_LDS = C > 32;
   const int n_lane = (wave % Split<C>::NWN) * 16 + (lane & 15);
-  const float bias_a = a.b[0][n_lane], bias_b = a.b[1][n_lane];
+  const float bias_a = TBase::of(a.b[0]).ldf((unsigned)n_lane * 4u), bias_b = TBase::of(a.b[1]).ldf((unsigned)n_lane * 4u);
   const int pos = ring_pos(a.in, hop);
+  // (the state block's bases sit (T - 6) and (T - HC_ROWS) frames BELOW the histories: a lane's offset is then that of frame t0 >= 0,
+  //  and the frame of the tile's row e a compile-time distance on top -- only rows at or past the history's first frame are written)
+  const TBase gin = ring_wg(a.in, b0), gsb = state_wg(a, b0, TS_B - (T - 6) * C), gsc = state_wg(a, b0, TS_C - (T - HC_ROWS) * C);
   float keep[n_pass<C, T, S>()][2][Split<C>::CT][4];
   layer<C, C, 3, 1, T, S, (C <= 32 ? 1 : 2)>(X, bfa, n_rows, wave, lane, keep,
     [&](int s, int t0, int n, int, float (&res)[4]) {
       if constexpr (RAG) {
         if (shop[s] < 0) { res[0] = res[1] = res[2] = res[3] = 0.0f; return; }   // (a stream that sits the step out: its rows compute on zeros, nothing of it is written)
       }
-      const float* p = ring_frame(a.in, b0 + s, stream_pos<RAG>(a.in, pos, shop, s), t0 + fb) + n;   // (frames t0 .. t0 + 3 of a step are contiguous in its ring slot)
+      const unsigned p = ring_off(a.in, s, stream_pos<RAG>(a.in, pos, shop, s), t0 + fb, n);   // (frames t0 .. t0 + 3 of a step are contiguous in its ring slot)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) res[e] = p[e * C];
+      for (int e = 0; e < 4; ++e) res[e] = gin.ldf(p, e * C * 4);
     },
     [&](int s, int t0, int n, int, const tail_f32x4& acc, float (&res)[4]) {
       float* yo = Y + row_off<C, T>(s, t0) + n;
-      float* st = a.state + (size_t)(b0 + s) * TAIL_STATE_FLOATS + TS_B + (t0 - (T - 6)) * C + n;
+      const unsigned st = (unsigned)(s * TAIL_STATE_FLOATS + t0 * C + n) * 4u;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float y = res[e] + (acc[e] + bias_a);
         yo[e * cs<C>()] = lrelu_max(y);
         if (IN_LDS) yr[((s * T) + t0 + e) * C + n] = y; else res[e] = y;   // the second layer's residual
-        if (last && t0 + e >= T - 6 && (!RAG || shop[s] >= 0)) st[e * C] = y;
+        if (last && t0 + e >= T - 6 && (!RAG || shop[s] >= 0)) gsb.stf(st, e * C * 4, y);
       }
     });
   after_a();
@@ -428,12 +466,12 @@ __device__ __forceinline__ void two_res_layers(const StageArgs& a, const int hop
     },
     [&](int s, int t0, int n, int, const tail_f32x4& acc, float (&res)[4]) {
       float* xo = X + row_off<C, T>(s, t0) + n;
-      float* st = a.state + (size_t)(b0 + s) * TAIL_STATE_FLOATS + TS_C + (t0 - (T - HC_ROWS)) * C + n;
+      const unsigned st = (unsigned)(s * TAIL_STATE_FLOATS + t0 * C + n) * 4u;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float z = res[e] + (acc[e] + bias_b);
         xo[e * cs<C>()] = lrelu_max(z);
-        if (last && t0 + e >= T - HC_ROWS && (!RAG || shop[s] >= 0)) st[e * C] = z;
+        if (last && t0 + e >= T - HC_ROWS && (!RAG || shop[s] >= 0)) gsc.stf(st, e * C * 4, z);
       }
     });
   TST_STAMP(5);
@@ -446,7 +484,14 @@ __device__ __forceinline__ void two_res_layers(const StageArgs& a, const int hop
 // into the next stage's ring.  IN_FROM_RING_HISTORY: the first layer's two history frames come from the input ring itself
 // (T1: the ring of up2 keeps them); otherwise from the state block at TS_IN (T2).
 template <int C, int T, int S, int COUT, int UPR, int TS_IN, int TS_B, int TS_C, bool IN_FROM_RING_HISTORY, bool RAG = false, int NSUB = 1>
-__device__ __forceinline__ void res_res_up_body(const StageArgs& a, const int g, float* __restrict__ lds) {
+__device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const int g, float* __restrict__ lds) {
+#if TST_GLOBAL
+  StageArgs a = a_table;   // (scalars: the block never leaves registers)
+  globalize(a);
+  a.hop = a_table.hop;     // (the tick launch's immediate: left as it is, so that stepc::step() still folds to its bits)
+#else
+  const StageArgs& a = a_table;
+#endif
   // (T = frames per SUB-step; the step has NSUB * T frames per stream, prologue())
   constexpr int NUP = UPR * COUT;
   float* X = lds;
@@ -482,16 +527,17 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a, const int g,
       using SU = Split<NUP>;
       float bias_u[SU::CT];
 #pragma unroll
-      for (int ct = 0; ct < SU::CT; ++ct) bias_u[ct] = a.b[2][(SU::POW2 ? wave % SU::NWN : ct) * 16 + (lane & 15)];
+      for (int ct = 0; ct < SU::CT; ++ct) bias_u[ct] = TBase::of(a.b[2]).ldf((unsigned)((SU::POW2 ? wave % SU::NWN : ct) * 16 + (lane & 15)) * 4u);
       const int pos_o = ring_pos(a.out, hop);
+      const TBase gout = ring_wg(a.out, b0);
       float none[n_pass<NUP, T, S>()][2][SU::CT][4];   // (no residual in this layer: never read, costs no registers)
       layer<C, NUP, 2, 1, T, S, 0>(X, bfu, n_rows, wave, lane, none, [](int, int, int, int, float (&)[4]) {},
         [&](int s, int t0, int n, int ct, const tail_f32x4& acc, float (&)[4]) {
           const float bu = bias_u[ct];   // (ct is a compile-time index after unrolling)
           if constexpr (RAG) { if (shop[s] < 0) return; }
-          float* o = ring_frame(a.out, b0 + s, stream_pos<RAG>(a.out, pos_o, shop, s), (t0 + fb) * UPR + n / COUT) + n % COUT;   // (output frames of one input frame are UPR apart)
+          const unsigned o = ring_off(a.out, s, stream_pos<RAG>(a.out, pos_o, shop, s), (t0 + fb) * UPR + n / COUT, n % COUT);   // (output frames of one input frame are UPR apart)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e * UPR * COUT] = acc[e] + bu;
+          for (int e = 0; e < 4; ++e) gout.stf(o, e * UPR * COUT * 4, acc[e] + bu);
         });
     }
     TST_STAMP(7);
@@ -564,7 +610,14 @@ constexpr int kT3Lds = t3_lds<kT3Streams, 1>();
 // ---------------------------------------------------------------------------------------------------------------------
 // T3: res4a, res4b (16 channels, 240 frames per stream) and the output conv: lrelu, Conv1d(16 -> 1, k7), tanh.
 template <bool RAG = false, int S = kT3Streams, int HOPS = 1, int NSUB = 1>
-__device__ __forceinline__ void t3_body(const StageArgs& a, const int g, float* __restrict__ lds) {
+__device__ __forceinline__ void t3_body(const StageArgs& a_table, const int g, float* __restrict__ lds) {
+#if TST_GLOBAL
+  StageArgs a = a_table;
+  globalize(a);
+  a.hop = a_table.hop;
+#else
+  const StageArgs& a = a_table;
+#endif
   static_assert(HOPS % NSUB == 0, "whole hops per sub-step");
   constexpr int C = 16, T = 240 * HOPS / NSUB;   // T = frames per SUB-step (prologue()): what the LDS holds
   static_assert(S * T <= NTHR, "one thread per output sample");
@@ -580,8 +633,8 @@ __device__ __forceinline__ void t3_body(const StageArgs& a, const int g, float* 
   __builtin_amdgcn_s_setprio(TST_SETPRIO);
 #endif
   const int io = a.io_stride != 0 ? stepc::slot(a.hop) : 0;
-  float* __restrict__ d_out = a.d_out + (size_t)io * a.io_stride;
   const int b0 = g * S;
+  const TBase gd = TBase::of(a.d_out, ((long long)io * (long long)a.io_stride + (long long)b0 * (T * NSUB)) * 4);   // the workgroup's first stream in its I/O slot
   const int n_rows = (a.B - b0 < S ? a.B - b0 : S) * T;
   int* shop = reinterpret_cast<int*>(lds + stage_lds<C, T, S, 6>() - 8);
   stream_hops<S, RAG>(a, hop, b0, shop);
@@ -608,7 +661,7 @@ __device__ __forceinline__ void t3_body(const StageArgs& a, const int g, float* 
         for (int j = 0; j < 7; ++j)
 #pragma unroll
           for (int c = 0; c < 16; ++c) acc = bsp::fma(x[j * cs<C>() + c], FW[j * 16 + c], acc);
-        d_out[(size_t)(b0 + s) * (T * NSUB) + fb + t] = bsp::tanh2(bsp::splat2(acc + fin_b)).x;   // (the packed form is the shorter one even for a single value)
+        gd.stf((unsigned)(s * (T * NSUB) + fb + t) * 4u, 0, bsp::tanh2(bsp::splat2(acc + fin_b)).x);   // (the packed form is the shorter one even for a single value)
       }
     }
     if constexpr (NSUB > 1) {
