@@ -155,9 +155,6 @@ __device__ __forceinline__ void run_type(const Banks<M, Rest...>& b, const Span&
     if (Op::NTHR >= NTHR || (int)threadIdx.x < Op::NTHR) {
       typename Op::Args a = b.a[sp.arg];   // (uniform: scalar loads)
       if constexpr (!RAG) stepc::set_hop(a, hop_imm, 0);   // the stage's {step counter, I/O slot} as an immediate (ring.h stepc)
-#ifdef FUSE_GLOBALIZE   // A/B build switch, OFF: the table's pointers told to be global memory (ring.h as_global) turn the launch's 2 271
-      globalize(a);         // flat loads into global loads with pipelined waits -- and the tick got 4 % SLOWER (profiles/r04_notes.md section 1)
-#endif
       Op::template run_t<RAG>(a, id % sp.gx, id / sp.gx, lds);
     }
   } else {

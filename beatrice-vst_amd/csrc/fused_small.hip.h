@@ -53,11 +53,6 @@ __device__ __forceinline__ float acquire(const unsigned long long* g, const int 
 }
 }  // namespace glink
 
-__device__ __forceinline__ void globalize(GruArgs& a) {
-  globalize(a.x); globalize(a.h);
-  a.wih = as_global(a.wih); a.whh = as_global(a.whh); a.bih = as_global(a.bih); a.bhh = as_global(a.bhh); a.hop = as_global(a.hop);
-  a.link_out = as_global(a.link_out); a.link_in = as_global(a.link_in);
-}
 
 // RT = row tiles of 16 streams per workgroup: at 2 the wavefront's weight fragments (held in registers for the whole
 // reduction) feed two independent MFMA chains -- half the weight traffic per stream and twice the work per dependent step.

@@ -43,10 +43,6 @@ struct F1Args {
   int H;
   size_t io_stride;    // 0, or floats between the slots of a resident multi-step input buffer (batch.hip)
 };
-__device__ __forceinline__ void globalize(F1Args& a) {
-  a.d_in = as_global(a.d_in); globalize(a.audio); globalize(a.out); a.w = as_global(a.w); a.bias = as_global(a.bias);
-  a.hop = as_global(a.hop); a.hop_publish = as_global(a.hop_publish); a.hop_publish_wave = as_global(a.hop_publish_wave);
-}
 // grid (stream, hop-in-step).  Samples before the step come from the audio ring, the rest from d_in.
 constexpr int kF1LdsFloats = 168 + 10 * 64;
 // PACK streams per workgroup, 256 threads each (the tick launch runs 512-thread workgroups: two streams share one).
@@ -118,7 +114,6 @@ struct F1Op {
 };
 // two streams per 512-thread workgroup (H = 1): grid ((n_streams + 1) / 2, 1)
 struct F1Args2 { F1Args a; int n_streams; };
-__device__ __forceinline__ void globalize(F1Args2& a) { globalize(a.a); }
 struct F1Op2 {
   using Args = F1Args2;
   static constexpr int NTHR = 512;
@@ -141,9 +136,6 @@ struct VqArgs {
   const float* const* cnorm;   // per row: [512]
   const int* k;                // per stream
 };
-__device__ __forceinline__ void globalize(VqArgs& a) {
-  globalize(a.raw); globalize(a.out); a.hop = as_global(a.hop); a.cbT = as_global(a.cbT); a.cnorm = as_global(a.cnorm); a.k = as_global(a.k);
-}
 constexpr int kVqLdsFloats = B_PHONE_CH + 8 + 8 + 8;
 template <bool RAG = false>
 __device__ __forceinline__ void phone_vq_body(const VqArgs& a, const int row, float* __restrict__ lds) {
@@ -305,10 +297,6 @@ struct FftArgs {
   int H;
   size_t io_stride;  // see F1Args
 };
-__device__ __forceinline__ void globalize(FftArgs& a) {
-  a.d_in = as_global(a.d_in); globalize(a.audio); globalize(a.spec); a.window = as_global(a.window); a.twiddle = as_global(a.twiddle);
-  a.hop = as_global(a.hop);
-}
 // Round 5: the same butterflies (MODEL_SPEC 4.2.1, operation for operation, the same twiddle table: bit-identical), scheduled as FIVE
 // passes of two stages each instead of ten passes through LDS.  A thread owns the four elements {base + m h1} of a pass (h1 = 4^p)
 // and runs the stage-h1 and the stage-2 h1 butterflies on them in registers.  Pass 0 takes its elements straight from the audio
@@ -419,7 +407,6 @@ struct FftOp {
   __device__ static __forceinline__ void run(const Args& a, int bx, int by, float* lds) { pitch_fft_body(a, bx, by, lds); }
 };
 struct FftArgs2 { FftArgs a; int n_streams; };
-__device__ __forceinline__ void globalize(FftArgs2& a) { globalize(a.a); }
 struct FftOp2 {  // two streams per 512-thread workgroup (H = 1): grid ((n_streams + 1) / 2, 1)
   using Args = FftArgs2;
   static constexpr int NTHR = 512;
@@ -457,11 +444,6 @@ struct PitchHeadArgs {
   float* host_out;      // 1-stream ABI (B = 1, H = 1) or null: pinned host block [4 feat | raw bin | sequence word]; the kernel writes the results there itself and the
                         // call's sequence word (mailbox word 3 behind the audio) LAST, behind a system-scope fence: the host polls that word, no copy command, no stream query
 };
-__device__ __forceinline__ void globalize(PitchHeadArgs& a) {
-  globalize(a.logits); globalize(a.h); a.d_in = as_global(a.d_in); a.voi_w = as_global(a.voi_w); a.voi_b = as_global(a.voi_b);
-  a.min_q = as_global(a.min_q); a.max_q = as_global(a.max_q); a.prev_q = as_global(a.prev_q); a.q_raw = as_global(a.q_raw);
-  a.q_out = as_global(a.q_out); a.feat = as_global(a.feat); a.params = as_global(a.params); a.hop = as_global(a.hop);
-}
 
 __device__ inline double pitch_round_half_away(double v) { return v >= 0.0 ? floor(v + 0.5) : -floor(-v + 0.5); }
 
@@ -601,11 +583,6 @@ struct CondArgs {
   int n_bins;          // rows of pitch_emb: 448, or 384 in the legacy generations -- which also have no formant table
                        // (frm_tab == nullptr): their conditioning is the ONE row add_tab[add_idx] the host hands over per hop
 };
-__device__ __forceinline__ void globalize(CondArgs& a) {
-  a.q = as_global(a.q); a.feat = as_global(a.feat); a.pitch_emb = as_global(a.pitch_emb); a.feat_w = as_global(a.feat_w);
-  a.add_tab = as_global(a.add_tab); a.add_idx = as_global(a.add_idx); a.frm_tab = as_global(a.frm_tab); a.frm_idx = as_global(a.frm_idx);
-  globalize(a.e); a.hop = as_global(a.hop); a.hop_next_out = as_global(a.hop_next_out);
-}
 template <bool RAG = false>
 __device__ __forceinline__ void wave_cond_body(const CondArgs& a, const int row, const int n = threadIdx.x) {
   const int b = row / a.H;

@@ -22,9 +22,9 @@ struct Ring {
 // so every wait for an LDS operand (s_waitcnt lgkmcnt(0): flat and LDS results return out of order) also waits for every
 // weight prefetch in flight.  A round trip through address space 1 tells the compiler what it is (InferAddressSpaces then
 // emits global_load / global_store with their own counter and the ISA shows the intended `s_waitcnt vmcnt(8) lgkmcnt(7)`).
-// MEASURED (round 4, same box, A/B) for EVERY pointer of EVERY body (globalize() below, -DFUSE_GLOBALIZE): the tick launch is
-// 4 % SLOWER with it (69.2 vs 66.5 us at 256 streams, 241 vs 232 us at 1 024) -- VGPR spills 48 -> 112 in the table kernel.
-// That switch stays off.  The NARROW form is on, inside the bodies themselves and with FEWER registers, not more: a wave-uniform
+// MEASURED (round 4, same box, A/B) for EVERY pointer of EVERY body: the tick launch is 4 % SLOWER with it (69.2 vs 66.5 us at
+// 256 streams, 241 vs 232 us at 1 024) -- VGPR spills 48 -> 112 in the table kernel (profiles/r04_notes.md section 1).
+// What is on is the NARROW form, inside the bodies themselves and with FEWER registers, not more: a wave-uniform
 // base made global in SCALAR registers plus one 32-bit lane offset (WGlobal / GBase below): no VGPR pair per address, the base
 // advanced by scalar adds, counted vmcnt waits, and LDS waits that leave the prefetch in flight.  First the weight stream and the
 // row gather of the GEMM bodies' segment loops (rowchain.hip.h WGlobal, load_tile, conv_rows_body's load_seg): same-box A/B at
@@ -111,7 +111,7 @@ struct WGlobal {
     return make_float4(v[0], v[1], v[2], v[3]);
   }
 };
-// globalize(args): every pointer of an argument block through as_global (one overload per block type, next to its struct)
+// globalize(args): every pointer of an argument block through as_global (the tail stages' StageArgs, tail_stages.hip.h)
 __device__ __forceinline__ void globalize(Ring& r) { r.base = as_global(r.base); }
 
 __host__ __device__ inline int ring_frames(const Ring& r) { return r.n * r.m; }

@@ -25,15 +25,6 @@
 #include "ring.h"
 #include "spec_math.hip.h"
 
-// Measurement aid (tools/debug/build_variant.sh ... -DABL_WEIGHTS_HOT): every weight-fragment prefetch re-reads the segment's
-// first k-blocks, so the weight stream hits the CU's L1 -- results are WRONG; the build exists to time the launch without
-// its L2 / Infinity Cache weight traffic.  Never defined in the product build.
-#ifdef ABL_WEIGHTS_HOT
-#define ABL_KB(x) ((x) & 1)
-#else
-#define ABL_KB(x) (x)
-#endif
-
 // per-phase cycle stamps of the attention bodies for tools/microbench/blockb_timing.hip (never defined in the product build)
 #ifdef RC_TIMING
 __device__ unsigned long long* g_rc_stamps;   // [workgroups][16]
@@ -50,48 +41,33 @@ constexpr int NTHR = 512, NWAVE = 8;
 // lane's q = l >> 4) are ONE ds_read_b128 instead of four ds_read_b32 (round 5; profiles/r05_notes.md).  Row stride = K + 8
 // floats: stride / 4 = 2 (mod 16) makes the 16-byte slots of each of ds_read_b128's four lane groups ({0-3, 12-15, 20-27}, ...:
 // rows 0-3 and 12-15 at one q, rows 4-11 at q + 1) all distinct -- conflict-free (with K + 4 rows 11 and 12 would collide).
-#ifndef RC_KPERM
-#define RC_KPERM 1   // A/B build switch: 0 = tiles in logical k order, four ds_read_b32 per k-block (rounds 2-4), row stride K + 2
-#endif
-constexpr bool KPERM = RC_KPERM != 0;
-constexpr int AS = B_HID + (KPERM ? 8 : 2);        // LDS row stride of a 256-channel tile
+// (Rounds 2-4 kept the tiles in logical k order, four ds_read_b32 per k-block; the comparison is in profiles/r05_notes.md.)
+constexpr int AS = B_HID + 8;        // LDS row stride of a 256-channel tile
 constexpr int TILE = 16 * AS;        // floats of one [16][256] tile
-constexpr int SS = B_KV_LEN + (KPERM ? 8 : 2);     // row stride of the score tile
+constexpr int SS = B_KV_LEN + 8;     // row stride of the score tile
 constexpr int STILE = 16 * SS;
-__host__ __device__ constexpr int kpos(int k) { return KPERM ? ((k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3)) : k; }
-constexpr int KSTEP = KPERM ? 4 : 1;   // distance of columns n, n + 1 of a lane's four inside a tile row
+__host__ __device__ constexpr int kpos(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
+constexpr int KSTEP = 4;   // distance of columns n, n + 1 of a lane's four inside a tile row
 // Which 16-byte piece (row r, floats 4 q .. 4 q + 3) of a [rows][256] tile a thread gathers: wave-load W (64 threads) and lane ln.
-// Logical tiles: one row per wave-load.  k-permuted tiles: FOUR rows x 16 pieces per wave-load -- a piece is stored as four
-// ds_write_b32 at p, p + 4, p + 8, p + 12, and 64 pieces of ONE row would hit 8 of the 32 banks (4-way, twice the time); rows
-// are 8 banks apart, so four rows x 16 pieces are 2-way, which costs a ds_write_b32 nothing (MI355X_MICROARCH.md, LDS)
-#ifndef RC_WMAP
-#define RC_WMAP RC_KPERM
-#endif
+// FOUR rows x 16 pieces per wave-load -- a piece is stored as four ds_write_b32 at p, p + 4, p + 8, p + 12, and 64 pieces of
+// ONE row would hit 8 of the 32 banks (4-way, twice the time); rows are 8 banks apart, so four rows x 16 pieces are 2-way,
+// which costs a ds_write_b32 nothing (MI355X_MICROARCH.md, LDS)
 template <int ROWGROUPS /* rows / 4 */>
 __device__ __forceinline__ void piece_of(const int W, const int ln, int* r, int* q) {
-  if constexpr (RC_WMAP != 0) { *r = 4 * (W % ROWGROUPS) + (ln >> 4); *q = 16 * (W / ROWGROUPS) + (ln & 15); }
-  else { *r = W; *q = ln; }
+  *r = 4 * (W % ROWGROUPS) + (ln >> 4); *q = 16 * (W / ROWGROUPS) + (ln & 15);
 }
 // a lane's operand base inside a tile row: its q = l >> 4
-__device__ __forceinline__ int lane_koff(const int lane) { return KPERM ? 4 * (lane >> 4) : (lane >> 4); }
-// the four values k = q, 4 + q, 8 + q, 12 + q of k-block kb for this lane (p = row base + lane_koff)
-__device__ __forceinline__ float4 lds_kblock(const float* __restrict__ p, const int kb) {
-  if constexpr (KPERM) return *reinterpret_cast<const float4*>(p + kb * 16);
-  else { const float* q = p + kb * 16; return make_float4(q[0], q[4], q[8], q[12]); }
-}
+__device__ __forceinline__ int lane_koff(const int lane) { return 4 * (lane >> 4); }
+// the four values k = q, 4 + q, 8 + q, 12 + q of k-block kb for this lane (p = row base + lane_koff): one ds_read_b128
+__device__ __forceinline__ float4 lds_kblock(const float* __restrict__ p, const int kb) { return *reinterpret_cast<const float4*>(p + kb * 16); }
 // Results come TRANSPOSED out of the matrix unit: the weights are the MFMA's A operand, the activations its B operand (bit for
 // bit the same chains: tools/microbench/mfma_swap.hip), so a lane owns FOUR CONSECUTIVE COLUMNS n0 .. n0 + 3 of ONE row (row =
 // l & 15, n0 = 16 tile + 4 (l >> 4)) -- one row lookup, one 16-byte bias / residual load and one 16-byte store per accumulator,
 // where the other orientation (four rows of one column) paid all of that per element.  In a k-permuted LDS tile those four
 // columns are the elements p, p + 4, p + 8, p + 12 with p = kpos(n0).
 __device__ __forceinline__ void store_perm4(float* __restrict__ row, const int n0, const float v0, const float v1, const float v2, const float v3) {
-  if constexpr (KPERM) {
-    float* d = row + kpos(n0);
-    d[0] = v0; d[4] = v1; d[8] = v2; d[12] = v3;
-  } else {   // (row stride K + 2: 8-byte aligned)
-    float2* d = reinterpret_cast<float2*>(row + n0);
-    d[0] = make_float2(v0, v1); d[1] = make_float2(v2, v3);
-  }
+  float* d = row + kpos(n0);
+  d[0] = v0; d[4] = v1; d[8] = v2; d[12] = v3;
 }
 
 // One reduction segment (KB k-blocks of 16) for CG column tiles of this wavefront: acc[c] += (A[16 x 16 KB] . W)^T.
@@ -105,18 +81,10 @@ __device__ __forceinline__ void store_perm4(float* __restrict__ row, const int n
 // s_waitcnt vmcnt(0); v_mfma` throughout, and a wavefront's MFMA density was ~27 %.  A __builtin_amdgcn_sched_barrier(0)
 // between "issue the loads of k-block i + D (weights) and i + 1 (A operand)" and "the MFMAs of k-block i" forbids that: loads
 // may still float among the MFMAs of the PREVIOUS k-block, never behind the ones that were meant to hide them.
-#ifndef RC_PIN_PIPELINE
-#define RC_PIN_PIPELINE 1
-#endif
 __device__ __forceinline__ void pin_pipeline() {
-#if RC_PIN_PIPELINE
   asm volatile("" ::: "memory");        // IR level: optimisation passes hoist invariant weight loads across a bare sched_barrier call
   __builtin_amdgcn_sched_barrier(0);    // machine scheduler: nothing crosses
-#endif
 }
-#ifndef RC_PREFETCH
-#define RC_PREFETCH 8
-#endif
 // Where a wavefront's weight fragments come from.  A fragment's address is WAVE-UNIFORM (layer, column tile, k-block) plus lane x 16
 // bytes, and the segment loops take it in exactly that form (WGlobal): the uniform base as a GLOBAL pointer in scalar registers
 // (ring.h as_global), the lane's part as one 32-bit byte offset shared by every column tile.  The loads are then global_load off a
@@ -146,71 +114,25 @@ using WStream = WLane;
 // loop's first fragment wait, while behind them it has D k-blocks of MFMAs as cover and its wait stays the one in front of its use
 struct NoGather { __device__ __forceinline__ void operator()() const {} };
 // prefetch depth of a segment in k-blocks (registers: D * CG float4)
-template <int RT, int CG> __host__ __device__ constexpr int seg_depth() { return RT == 1 ? (CG <= 2 ? RC_PREFETCH : (CG <= 3 ? 4 : 2)) : (RT * CG <= 2 ? 8 : 4); }
-// the first seg_depth() k-blocks of a segment's weight fragments, requested by the CALLER ahead of time (a body's first segment: the
-// request goes out before the body gathers its rows, so that the two round trips overlap instead of following each other)
-template <int RT, int CG> struct SegHead { float4 v[seg_depth<RT, CG>()][CG]; };
-template <int RT, int CG, class W>
-__device__ __forceinline__ void seg_head_load(SegHead<RT, CG>& h, const W (&wf)[CG]) {
-#pragma unroll
-  for (int d = 0; d < seg_depth<RT, CG>(); ++d)
-#pragma unroll
-    for (int c = 0; c < CG; ++c) h.v[d][c] = wf[c].kblock(d);
+template <int RT, int CG> __host__ __device__ constexpr int seg_depth() {
+  constexpr int PREFETCH = 8;   // one row tile, up to two column tiles
+  return RT == 1 ? (CG <= 2 ? PREFETCH : (CG <= 3 ? 4 : 2)) : (RT * CG <= 2 ? 8 : 4);
 }
+// RT row tiles of 16 share every B fragment (tile t's operand base = a + t * a_tile_stride): acc[t][c] += A_t . W_c.
+// A fragment then feeds RT MFMAs: half the weight traffic per multiply-add at RT = 2.
 // (D: the prefetch depth, seg_depth() in the product; a parameter for tools/microbench/seg_loop.hip's sweep)
-template <int CG, int KB, bool HEAD = false, int D = seg_depth<1, CG>(), class W, class Gather = NoGather>
-__device__ __forceinline__ void mma_segment_p(f32x4 (&acc)[CG], const float* __restrict__ a, const W (&wf)[CG], const SegHead<1, CG>* head = nullptr,
-                                              Gather gather = Gather()) {
+template <int RT, int CG, int KB, int D = seg_depth<RT, CG>(), class W, class Gather = NoGather>
+__device__ __forceinline__ void mma_segment_rt(f32x4 (&acc)[RT][CG], const float* __restrict__ a, const int a_tile_stride,
+                                               const W (&wf)[CG], Gather gather = Gather()) {
   static_assert(KB % D == 0, "segment length");
-  static_assert(!HEAD || D == seg_depth<1, CG>(), "a SegHead holds seg_depth() k-blocks");
   float4 bq[D][CG];
   pin_pipeline();   // (the segment's first loads stay behind what precedes it: hoisted over an epilogue they only add register pressure)
 #pragma unroll
   for (int d = 0; d < D; ++d)
 #pragma unroll
-    for (int c = 0; c < CG; ++c) { if constexpr (HEAD) bq[d][c] = head->v[d][c]; else bq[d][c] = wf[c].kblock(d); }
+    for (int c = 0; c < CG; ++c) bq[d][c] = wf[c].kblock(d);
   gather();
-  float4 an = lds_kblock(a, 0);   // activations of the k-block to come (one k-block ahead: LDS latency behind 4 CG MFMAs), one ds_read_b128
-#pragma unroll
-  for (int kb = 0; kb < KB; kb += D) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      float4 cur[CG];
-#pragma unroll
-      for (int c = 0; c < CG; ++c) cur[c] = bq[d][c];
-      const float4 x = an;
-      if (kb + d + D < KB) {
-#pragma unroll
-        for (int c = 0; c < CG; ++c) bq[d][c] = wf[c].kblock(ABL_KB(kb + d + D));
-      }
-      if (kb + d + 1 < KB) an = lds_kblock(a, kb + d + 1);
-      pin_pipeline();
-#pragma unroll
-      for (int c = 0; c < CG; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur[c].x, x.x, acc[c], 0, 0, 0);
-#pragma unroll
-      for (int c = 0; c < CG; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur[c].y, x.y, acc[c], 0, 0, 0);
-#pragma unroll
-      for (int c = 0; c < CG; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur[c].z, x.z, acc[c], 0, 0, 0);
-#pragma unroll
-      for (int c = 0; c < CG; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur[c].w, x.w, acc[c], 0, 0, 0);
-    }
-  }
-}
-// The same for RT row tiles of 16 that share every B fragment (a1 = a0 + one LDS tile): acc[t][c] += A_t . W_c.
-// A fragment then feeds RT MFMAs: half the weight traffic per multiply-add at RT = 2.
-template <int RT, int CG, int KB, bool HEAD = false, int D = seg_depth<RT, CG>(), class W, class Gather = NoGather>
-__device__ __forceinline__ void mma_segment_rt(f32x4 (&acc)[RT][CG], const float* __restrict__ a, const int a_tile_stride,
-                                               const W (&wf)[CG], const SegHead<RT, CG>* head = nullptr, Gather gather = Gather()) {
-  static_assert(KB % D == 0, "segment length");
-  static_assert(!HEAD || D == seg_depth<RT, CG>(), "a SegHead holds seg_depth() k-blocks");
-  float4 bq[D][CG];
-  pin_pipeline();
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-#pragma unroll
-    for (int c = 0; c < CG; ++c) { if constexpr (HEAD) bq[d][c] = head->v[d][c]; else bq[d][c] = wf[c].kblock(d); }
-  gather();
-  float4 an[RT];
+  float4 an[RT];   // activations of the k-block to come (one k-block ahead: LDS latency behind 4 RT CG MFMAs), one ds_read_b128 per tile
 #pragma unroll
   for (int t = 0; t < RT; ++t) an[t] = lds_kblock(a + t * a_tile_stride, 0);
 #pragma unroll
@@ -225,7 +147,7 @@ __device__ __forceinline__ void mma_segment_rt(f32x4 (&acc)[RT][CG], const float
       for (int t = 0; t < RT; ++t) av[t] = an[t];
       if (kb + d + D < KB) {
 #pragma unroll
-        for (int c = 0; c < CG; ++c) bq[d][c] = wf[c].kblock(ABL_KB(kb + d + D));
+        for (int c = 0; c < CG; ++c) bq[d][c] = wf[c].kblock(kb + d + D);
       }
       if (kb + d + 1 < KB) {
 #pragma unroll
@@ -257,7 +179,7 @@ __device__ __forceinline__ void mma_segment(f32x4 (&acc)[CG], const float* __res
   W wfc[CG];
 #pragma unroll
   for (int c = 0; c < CG; ++c) wfc[c] = wf.at(c * tile_stride);
-  mma_segment_p<CG, KB>(acc, a, wfc);
+  mma_segment_rt<1, CG, KB>(reinterpret_cast<f32x4 (&)[1][CG]>(acc), a, 0, wfc);   // (one row tile: f32x4[CG] is f32x4[1][CG])
 }
 
 // A layer over 16 rows: K = NSEG segments of 256 (segment s read from LDS tile seg[s], row stride `as`), N = 16 * 8 * CG
@@ -314,10 +236,6 @@ struct BlockAArgs {
   const int* hop;
   int B;
 };
-__device__ __forceinline__ void globalize(BlockAArgs& a) {
-  globalize(a.x); globalize(a.xa);
-  a.c1_w = as_global(a.c1_w); a.c1_b = as_global(a.c1_b); a.c2_w = as_global(a.c2_w); a.c2_b = as_global(a.c2_b); a.hop = as_global(a.hop);
-}
 constexpr int kBlockALds = 4 * TILE + 32;   // + sid[16], rowhop[16]
 template <int D, bool RAG = false, int HOPS = 1>
 __device__ __forceinline__ void block_a_body(const BlockAArgs& a, const int g, float* __restrict__ lds) {
@@ -394,11 +312,6 @@ struct BlockBArgs {
   const int* tile_slot;            // [n_tiles]
   const int* hop;
 };
-__device__ __forceinline__ void globalize(BlockBArgs& a) {
-  globalize(a.xa); globalize(a.out);
-  a.q_w = as_global(a.q_w); a.q_b = as_global(a.q_b); a.o_w = as_global(a.o_w); a.o_b = as_global(a.o_b);
-  a.kt = as_global(a.kt); a.v = as_global(a.v); a.perm = as_global(a.perm); a.tile_slot = as_global(a.tile_slot); a.hop = as_global(a.hop);
-}
 constexpr int kBlockBLds = 2 * TILE + STILE + 48;   // + inv[16], sid[16], rowhop[16]
 template <bool RAG = false, int HOPS = 1>
 __device__ __forceinline__ void block_b_body(const BlockBArgs& a, const int g, float* __restrict__ lds) {
@@ -591,11 +504,6 @@ struct BlockBqArgs {
   const int* qslot;                      // [n_quads] slot or -1 (quad unused)
   const int* hop;
 };
-__device__ __forceinline__ void globalize(BlockBqArgs& a) {
-  globalize(a.xa); globalize(a.out);
-  a.q_w = as_global(a.q_w); a.q_b = as_global(a.q_b); a.o_w = as_global(a.o_w); a.o_b = as_global(a.o_b);
-  a.ktp = as_global(a.ktp); a.vp = as_global(a.vp); a.qperm = as_global(a.qperm); a.qslot = as_global(a.qslot); a.hop = as_global(a.hop);
-}
 constexpr int kBlockBqLds = kBlockBLds;
 template <bool RAG = false, int HOPS = 1>
 __device__ __forceinline__ void block_bq_body(const BlockBqArgs& a, const int g, float* __restrict__ lds) {
@@ -740,19 +648,12 @@ __device__ __forceinline__ void conv_rows_body(const ConvArgs& a, const int bx, 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hop = stepc::step(a.hop);
   if (hop < 0) return;
-  // the first thing a workgroup does: request the first weight fragments of its first segment -- that round trip then runs beside the
-  // row table's barrier and the row gather instead of behind them (a short body is mostly such round trips, profiles/r05_notes.md)
   WStream wfc[CG];
 #pragma unroll
   for (int c = 0; c < CG; ++c) {
     const int nt = wave + NWAVE * c < NTL ? wave + NWAVE * c : NTL - 1;  // surplus tiles of a ragged layer recompute the last one
     wfc[c] = WStream::make(reinterpret_cast<const float4*>(a.w) + (size_t)(nt_base + nt) * (K / 16) * 64, lane);
   }
-#ifndef RC_SEG_HEAD
-#define RC_SEG_HEAD 0   // A/B switch, OFF: 1 = the first segment's first weight fragments requested before the row gather -- measured 256 streams x 2 hops 118.1 -> 120.5 us (slower), x 4 hops 237.4 -> 236.4, x 1 hop unchanged (profiles/r05_notes.md)
-#endif
-  SegHead<RT, CG> head;
-  if constexpr (RC_SEG_HEAD != 0) seg_head_load<RT, CG>(head, wfc);
   const int M = a.B * L::T;
   const bool rag = stepc::rag_t<RAG>();   // (ragged tick step: every row at its stream's own counter; absent streams' rows drop out)
   if (tid < ROWS) {
@@ -794,6 +695,7 @@ __device__ __forceinline__ void conv_rows_body(const ConvArgs& a, const int bx, 
       store_perm4(dst + pr[i] * AS, 4 * pq[i], v.x, v.y, v.z, v.w);   // (row 16 t + r of the slot = row r of its tile t: tiles are contiguous)
     }
   };
+  // (requesting the first segment's first weight fragments BEFORE this gather measured slower: 256 streams x 2 hops 118.1 -> 120.5 us, profiles/r05_notes.md)
   load_seg(0);
   store_seg(slot[0]);
   __syncthreads();
@@ -811,21 +713,8 @@ __device__ __forceinline__ void conv_rows_body(const ConvArgs& a, const int bx, 
 #pragma unroll
     for (int c = 0; c < CG; ++c) wfs[c] = wfc[c].at((size_t)s * 16 * 64);
     const float* ap = slot[s & 1] + (lane & 15) * AS + lane_koff(lane);
-    if (RC_SEG_HEAD != 0 && s == 0) {   // (s is a compile-time index after unrolling)
-      if constexpr (RT == 1) {
-        if constexpr (P > 1) mma_segment_p<CG, 16, true>(acc[0], ap, wfs, &head, gather);
-        else mma_segment_p<CG, LAST / 16, true>(acc[0], ap, wfs, &head, gather);
-      } else {
-        if constexpr (P > 1) mma_segment_rt<RT, CG, 16, true>(acc, ap, TILE, wfs, &head, gather);
-        else mma_segment_rt<RT, CG, LAST / 16, true>(acc, ap, TILE, wfs, &head, gather);
-      }
-    } else if constexpr (RT == 1) {
-      if (s + 1 < P) mma_segment_p<CG, 16>(acc[0], ap, wfs, nullptr, gather);
-      else mma_segment_p<CG, LAST / 16>(acc[0], ap, wfs, nullptr, gather);
-    } else {
-      if (s + 1 < P) mma_segment_rt<RT, CG, 16>(acc, ap, TILE, wfs, nullptr, gather);
-      else mma_segment_rt<RT, CG, LAST / 16>(acc, ap, TILE, wfs, nullptr, gather);
-    }
+    if (s + 1 < P) mma_segment_rt<RT, CG, 16>(acc, ap, TILE, wfs, gather);
+    else mma_segment_rt<RT, CG, LAST / 16>(acc, ap, TILE, wfs, gather);
 #pragma unroll
     for (int t = 0; t < RT; ++t)
 #pragma unroll
@@ -904,7 +793,6 @@ struct NopOp {
   __device__ static __forceinline__ void run(const Args&, int, int, float*) {}
   template <bool RAG> __device__ static __forceinline__ void run_t(const Args&, int, int, float*) {}
 };
-__device__ __forceinline__ void globalize(NopOp::Args&) {}
 
 // the same body as a launch of its own (the in-order chain at large batches, wave.hip)
 template <class L, int COLS, int RT>

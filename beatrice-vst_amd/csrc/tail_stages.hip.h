@@ -151,9 +151,6 @@ __device__ __forceinline__ void fetch_b(const float* __restrict__ wpacked, float
 #endif
 }
 
-#ifndef TST_PIN
-#define TST_PIN 1
-#endif
 // One pass of a layer: NT (1 or 2, compile time) row tiles of 16 that share every B operand.  ap[u] = the lane's A pointer
 // of tile u: (row lane & 15 of the tile, LOWEST tap, k offset lane >> 4), so that every operand sits at a compile-time,
 // non-negative offset.  The reduction runs in groups of four MFMA steps (16 k = one B fragment record); the A operands of
@@ -186,10 +183,8 @@ __device__ __forceinline__ void pass(const float* const (&ap)[2], const float4 (
 #pragma unroll
         for (int u = 0; u < NT; ++u) xq[g % PD][e][u] = ap[u][a_off((g + PD) * 4 + e)];
     }
-#if TST_PIN
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -501,9 +496,6 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hop = stepc::step(a.hop);
   if (hop < 0) return;
-#ifdef TST_SETPRIO
-  __builtin_amdgcn_s_setprio(TST_SETPRIO);   // experiment: issue priority over the co-resident workgroup's wavefronts
-#endif
   const int b0 = g * S;
   const int n_rows = (a.B - b0 < S ? a.B - b0 : S) * T;
   int* shop = reinterpret_cast<int*>(lds + stage_lds<C, T, S, 1>() - 8);
@@ -629,9 +621,6 @@ __device__ __forceinline__ void t3_body(const StageArgs& a_table, const int g, f
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hop = stepc::step(a.hop);
   if (hop < 0) return;
-#ifdef TST_SETPRIO
-  __builtin_amdgcn_s_setprio(TST_SETPRIO);
-#endif
   const int io = a.io_stride != 0 ? stepc::slot(a.hop) : 0;
   const int b0 = g * S;
   const TBase gd = TBase::of(a.d_out, ((long long)io * (long long)a.io_stride + (long long)b0 * (T * NSUB)) * 4);   // the workgroup's first stream in its I/O slot

@@ -67,28 +67,13 @@ using namespace wave_layers;
 // LDS one 256-long reduction segment at a time, weights prefetched four to eight k-blocks ahead.  A tick wants MFMA density
 // and occupancy, not the shortest dependent chain: per-layer launches with 16x32 tiles and 128-wide k-chunks (the in-order
 // chain's choice) measured 0.224 ms per tick at 256 streams, 16x64 tiles in 256-thread workgroups 0.104, this layout 0.078.
-// (A/B build switches; measured at 256 / 1024 streams: one row tile, full width 3.18 / 3.83 M frames/s; the three long
+// (Measured at 256 / 1024 streams: one row tile, full width 3.18 / 3.83 M frames/s; the three long
 //  layers as 32 rows x 128 columns 3.27 / 3.85; every conv_rows body with two row tiles 3.29 / 3.98)
-#ifndef TICK_RB_COLS
-#define TICK_RB_COLS 128
-#endif
-#ifndef TICK_GRU_RT
-#define TICK_GRU_RT 2
-#endif
-#ifndef TICK_MID_RT
-#define TICK_MID_RT 2
-#endif
+constexpr int kRbCols = 128;   // column slab of the three long layers (f4, f5, rb)
+constexpr int kGruRt = 2, kMidRt = 2, kRbRt = 2, kP1Rt = kMidRt;   // row tiles of 16 per workgroup
 // (phone.f3 with ONE row tile: it runs in the launch's second round, where short workgroups matter more than traffic --
 //  32 workgroups of 28 us end the launch later than 64 of 18 us: 3.45 -> 3.55 M frames/s at 256 streams)
-#ifndef TICK_F3_RT
-#define TICK_F3_RT 1
-#endif
-#ifndef TICK_RB_RT
-#define TICK_RB_RT 2
-#endif
-#ifndef TICK_P1_RT
-#define TICK_P1_RT TICK_MID_RT
-#endif
+constexpr int kF3Rt = 1;
 
 enum BodyType {
   T_F1, T_FFT, T_F2, T_F3, T_F4, T_F5, T_P1, T_RB, T_P23, T_POUT, T_HEAD, T_OUT, T_COND, T_INP, T_UP1, T_RES1A, T_RES1B, T_UP2,
@@ -103,28 +88,28 @@ template <int H>
 struct Ops {
   using PL = PhoneLayers<H>;
   using QL1 = PitchLayers<H>;
-  using OpF2 = rc::ConvRowsOp<typename PL::F2, 0, TICK_MID_RT>;
-  using OpF3 = rc::ConvRowsOp<typename PL::F3, 0, TICK_F3_RT>;
-  using OpF4 = rc::ConvRowsOp<typename PL::F4, TICK_RB_COLS, TICK_RB_RT>;
-  using OpF5 = rc::ConvRowsOp<typename PL::F5, TICK_RB_COLS, TICK_RB_RT>;
-  using OpRB = rc::ConvRowsOp<typename PL::RBL, TICK_RB_COLS, TICK_RB_RT>;
+  using OpF2 = rc::ConvRowsOp<typename PL::F2, 0, kMidRt>;
+  using OpF3 = rc::ConvRowsOp<typename PL::F3, 0, kF3Rt>;
+  using OpF4 = rc::ConvRowsOp<typename PL::F4, kRbCols, kRbRt>;
+  using OpF5 = rc::ConvRowsOp<typename PL::F5, kRbCols, kRbRt>;
+  using OpRB = rc::ConvRowsOp<typename PL::RBL, kRbCols, kRbRt>;
   using OpOUT = rc::ConvRowsOp<typename PL::OUTL>;
-  using OpP1 = rc::ConvRowsOp<typename QL1::P1, 0, TICK_P1_RT>;
+  using OpP1 = rc::ConvRowsOp<typename QL1::P1, 0, kP1Rt>;
   using OpP23 = rc::ConvRowsOp<typename QL1::P23>;
   using OpPOUT = rc::ConvRowsOp<typename QL1::POUT>;
   using OpINP = rc::ConvRowsOp<INP<H>>;
-  using OpUP1 = rc::ConvRowsOp<UP<256, 128, 5, H>, 128, TICK_MID_RT>;   // 640 columns: five slabs
-  using OpRES1A = rc::ConvRowsOp<RES<128, 1, 5 * H>, 0, TICK_MID_RT>;
-  using OpRES1B = rc::ConvRowsOp<RES<128, 3, 5 * H>, 0, TICK_MID_RT>;
-  using OpUP2 = rc::ConvRowsOp<UP<128, 64, 4, 5 * H>, 0, TICK_MID_RT>;
+  using OpUP1 = rc::ConvRowsOp<UP<256, 128, 5, H>, 128, kMidRt>;   // 640 columns: five slabs
+  using OpRES1A = rc::ConvRowsOp<RES<128, 1, 5 * H>, 0, kMidRt>;
+  using OpRES1B = rc::ConvRowsOp<RES<128, 3, 5 * H>, 0, kMidRt>;
+  using OpUP2 = rc::ConvRowsOp<UP<128, 64, 4, 5 * H>, 0, kMidRt>;
   // The SPARSE table (the first ticks of a fill, while only front-end stages have a step): the bodies whose workgroups last longest
   // in half-size pieces -- one row tile per convolution workgroup (and half the streams per tail workgroup, unused: see tick_run).  A
   // partly filled launch lasts as long as its longest workgroup and has idle slots to spare, so shorter workgroups in larger
   // numbers are what it wants (in a full tick they cost ~3 %: twice the weight traffic per row, more prologues).  Same arithmetic,
   // same rings: a tick may use either table.
-  using OpF4s = rc::ConvRowsOp<typename PL::F4, TICK_RB_COLS, 1>;
-  using OpF5s = rc::ConvRowsOp<typename PL::F5, TICK_RB_COLS, 1>;
-  using OpRBs = rc::ConvRowsOp<typename PL::RBL, TICK_RB_COLS, 1>;
+  using OpF4s = rc::ConvRowsOp<typename PL::F4, kRbCols, 1>;
+  using OpF5s = rc::ConvRowsOp<typename PL::F5, kRbCols, 1>;
+  using OpRBs = rc::ConvRowsOp<typename PL::RBL, kRbCols, 1>;
   using OpP1s = rc::ConvRowsOp<typename QL1::P1, 0, 1>;
   using OpUP1s = rc::ConvRowsOp<UP<256, 128, 5, H>, 128, 1>;
   // the tail's stages: streams per workgroup so that a workgroup holds the same number of rows at every H (80 / 240 / 480; H = 2: T2 160).
@@ -143,12 +128,12 @@ struct Ops {
   // GruQ / GruP: hop 0 (publishes when H > 1); GruQm / GruPm: hops 1 .. H - 2 (poll and publish; H = 4: two of each, every link
   // its own granule array); GruQ1 / GruP1: the last hop (polls)
   static_assert(H <= 4, "link arrays: tick::State");
-  using GruQ = GruOp<128, 128, TICK_GRU_RT, (H > 1 ? 1 : 0)>;
-  using GruP = GruOp<256, 256, TICK_GRU_RT, (H > 1 ? 1 : 0)>;
-  using GruQ1 = std::conditional_t<H == 1, rc::NopOp, GruOp<128, 128, TICK_GRU_RT, 2>>;
-  using GruP1 = std::conditional_t<H == 1, rc::NopOp, GruOp<256, 256, TICK_GRU_RT, 2>>;
-  using GruQm = std::conditional_t<H <= 2, rc::NopOp, GruOp<128, 128, TICK_GRU_RT, 3>>;
-  using GruPm = std::conditional_t<H <= 2, rc::NopOp, GruOp<256, 256, TICK_GRU_RT, 3>>;
+  using GruQ = GruOp<128, 128, kGruRt, (H > 1 ? 1 : 0)>;
+  using GruP = GruOp<256, 256, kGruRt, (H > 1 ? 1 : 0)>;
+  using GruQ1 = std::conditional_t<H == 1, rc::NopOp, GruOp<128, 128, kGruRt, 2>>;
+  using GruP1 = std::conditional_t<H == 1, rc::NopOp, GruOp<256, 256, kGruRt, 2>>;
+  using GruQm = std::conditional_t<H <= 2, rc::NopOp, GruOp<128, 128, kGruRt, 3>>;
+  using GruPm = std::conditional_t<H <= 2, rc::NopOp, GruOp<256, 256, kGruRt, 3>>;
   using Vq = std::conditional_t<H == 1, VqOp, VqRowsOp<H>>;   // (several hops: a stream's rows in one workgroup, the codebook read once)
   template <class... Ms> struct List { using Tab = fuse::Table<Ms...>; using Builder = fuse::TableBuilder<Ms...>; };
   using L = List<

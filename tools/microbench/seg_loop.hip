@@ -1,4 +1,4 @@
-// The segment loops of the row-local bodies (rc::mma_segment_p / mma_segment_rt, rowchain.hip.h) ALONE: 512-thread workgroups,
+// The segment loop of the row-local bodies (rc::mma_segment_rt, rowchain.hip.h) ALONE: 512-thread workgroups,
 // two per CU, the A operand in k-permuted LDS tiles, the packed weights of a layer of the real size streaming past -- no row
 // gather from a ring, no epilogue beyond one store per accumulator.  What it answers: how far from the FP32-MFMA peak is the
 // loop by itself, and what do the form of the weight loads (rc::WLane: a per-lane generic pointer taken from a table in device
@@ -54,8 +54,7 @@ __global__ __launch_bounds__(512, 4) void seg_kernel(const SegArgs* tab) {
 #pragma unroll
     for (int c = 0; c < CG; ++c) wfs[c] = wfc[c].at((size_t)s * 16 * 64);
     const float* ap = lds + (s & 1) * RT * rc::TILE + (lane & 15) * rc::AS + rc::lane_koff(lane);
-    if constexpr (RT == 1) rc::mma_segment_p<CG, 16, false, D>(acc[0], ap, wfs);
-    else rc::mma_segment_rt<RT, CG, 16, false, D>(acc, ap, rc::TILE, wfs);
+    rc::mma_segment_rt<RT, CG, 16, D>(acc, ap, rc::TILE, wfs);
 #pragma unroll
     for (int t = 0; t < RT; ++t)
 #pragma unroll
