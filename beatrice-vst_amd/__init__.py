@@ -24,6 +24,7 @@ PRODUCT_LIB = os.environ.get("BEATRICE_HIP_LIB") or os.path.join(HERE, "csrc", "
 IN_HOP, OUT_HOP = 160, 240
 PHONE_CH, HID, PITCH_BINS = 128, 256, 448
 CODEBOOK, KV_LEN, KV_CH, N_BLOCKS = 512, 384, 128, 4
+STEP_WRAP = 12252240  # BEATRICE_HIP_STEP_WRAP (include/beatrice_batch.h): the step / hop counter wraps to 0 after STEP_WRAP - 1
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int)
@@ -163,18 +164,36 @@ class ModelsLegacy:
         a.DestroyWaveformGenerator(self.wave)
 
 
+def set_hop_count(fn, contexts, counter):
+    """The hop counters of a new stream's (phone, pitch, waveform) contexts through BeatriceHip_SetHopCount[Legacy] (kind 1, 2, 3)."""
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, _vp, C.c_int]
+    for kind, ctx in enumerate(contexts, 1):
+        if fn(kind, ctx, counter) != 0:
+            raise RuntimeError("hop counter %d refused (context kind %d)" % (counter, kind))
+
+
+def get_hop_counts(fn, contexts):
+    fn.restype, fn.argtypes = C.c_int, [C.c_int, _vp]
+    return tuple(int(fn(kind, ctx)) for kind, ctx in enumerate(contexts, 1))
+
+
 class StreamLegacy:
     """One stream through a legacy generation's per-hop protocol (reference src/common/processor_core_1.cc:50-143):
     phone, pitch, the host's pitch transform (clamped to [1, 383]), speaker vector = speaker + formant-shift row."""
 
-    def __init__(self, models, speaker=0, formant_index=4, min_q=1, max_q=LEGACY_PITCH_BINS - 1):
+    def __init__(self, models, speaker=0, formant_index=4, min_q=1, max_q=LEGACY_PITCH_BINS - 1, start_counter=None):
         self.m, self.a = models, models.abi
         a = self.a
         self.pc, self.tc, self.wc = a.CreatePhoneContext1(), a.CreatePitchContext1(), a.CreateWaveformContext1()
+        if start_counter is not None:  # test hook, product library only (BeatriceHip_SetHopCountLegacy)
+            set_hop_count(a.lib.BeatriceHip_SetHopCountLegacy, (self.pc, self.tc, self.wc), start_counter)
         self.speaker, self.formant_index = speaker, formant_index
         self.pitch_params = {}
         a.SetMinQuantizedPitch(self.tc, min_q)
         a.SetMaxQuantizedPitch(self.tc, max_q)
+
+    def hop_counts(self):
+        return get_hop_counts(self.a.lib.BeatriceHip_HopCountLegacy, (self.pc, self.tc, self.wc))
 
     def hop(self, x160, return_all=False):
         a, m = self.a, self.m
@@ -280,11 +299,13 @@ class Stream1:
     """One stream through the 1-stream C-ABI with the reference's per-hop call protocol
     (reference src/common/processor_core_2.cc:181-255 and :431-466)."""
 
-    def __init__(self, models, speaker=0, formant_index=4, vq_k=0, min_q=1, max_q=383):
+    def __init__(self, models, speaker=0, formant_index=4, vq_k=0, min_q=1, max_q=383, start_counter=None):
         self.m, a = models, models.abi
         self.a = a
         self.pc, self.tc = a.CreatePhoneContext1(), a.CreatePitchContext1()
         self.wc, self.ec = a.CreateWaveformContext1(), a.CreateEmbeddingContext()
+        if start_counter is not None:  # test hook, product library only: the new contexts' hop counters (BeatriceHip_SetHopCount)
+            set_hop_count(a.lib.BeatriceHip_SetHopCount, (self.pc, self.tc, self.wc), start_counter)
         self.kv_count = N_BLOCKS
         self.pitch_params = {}
         self.set_target_speaker(speaker)
@@ -294,6 +315,10 @@ class Stream1:
         a.SetMinQuantizedPitch(self.tc, min_q)
         a.SetMaxQuantizedPitch(self.tc, max_q)
         a.SetVQNumNeighbors(self.pc, vq_k)
+
+    def hop_counts(self):
+        """The hop counters of the (phone, pitch, waveform) contexts' next hops (product library only, BeatriceHip_HopCount)."""
+        return get_hop_counts(self.a.lib.BeatriceHip_HopCount, (self.pc, self.tc, self.wc))
 
     def set_target_speaker(self, s):
         t, a = self.m.tables, self.a
@@ -374,6 +399,12 @@ _BATCH = {
     "BeatriceHip_InjectTeamTimeoutPitch": (C.c_int, [_vp]),
     "BeatriceHip_PitchSpeculation": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "BeatriceBatch_InjectTeamTimeout": (C.c_int, [_vp]),
+    "BeatriceBatch_SetStepCounter": (C.c_int, [_vp, C.c_int]),
+    "BeatriceBatch_StepCounter": (C.c_int, [_vp]),
+    "BeatriceHip_SetHopCount": (C.c_int, [C.c_int, _vp, C.c_int]),
+    "BeatriceHip_SetHopCountLegacy": (C.c_int, [C.c_int, _vp, C.c_int]),
+    "BeatriceHip_HopCount": (C.c_int, [C.c_int, _vp]),
+    "BeatriceHip_HopCountLegacy": (C.c_int, [C.c_int, _vp]),
     "BeatriceHip_ModelBlob": (C.c_int, [C.c_int, _vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "BeatriceHip_ModelBlobReady": (C.c_int, [C.c_int, _vp]),
     "BeatriceBatch_Create": (_vp, [_vp, _vp, _vp, _vp, C.c_int, C.c_int]),
@@ -480,7 +511,7 @@ class Batch:
     hops_per_step = 1: one 10 ms hop per step (real time).  2 or 4: block mode, every step converts that
     many consecutive hops per stream (in [B][H*160] -> out [B][H*240]), same results as single hops."""
 
-    def __init__(self, models, n_streams, max_speakers=None, hops_per_step=1, upload_tables=True):
+    def __init__(self, models, n_streams, max_speakers=None, hops_per_step=1, upload_tables=True, start_counter=None):
         self.m = models
         self.a = bind_batch(models.abi)
         t = models.tables if upload_tables else None
@@ -496,6 +527,8 @@ class Batch:
                                                       hops_per_step)
         if not self.a.BeatriceBatch_IsHealthy(self.h):
             raise RuntimeError("BeatriceBatch_Create failed (no GPU / HIP error)")
+        if start_counter is not None:  # test hook: the new batch's step counter (BeatriceBatch_SetStepCounter)
+            self._check(self.a.BeatriceBatch_SetStepCounter(self.h, start_counter))
         if not upload_tables:  # the caller fills the device tables itself (shard.share_speaker_tables)
             return
         self._check(self.a.BeatriceBatch_SetSpeakerTables(self.h, t.n_speakers + 1, fptr(t.codebooks), fptr(t.additive),
@@ -513,6 +546,10 @@ class Batch:
     def _check(rc):
         if rc != 0:
             raise RuntimeError("BeatriceBatch call failed: %d" % rc)
+
+    def step_counter(self):
+        """The step counter of the next step (the host's mirror, BeatriceBatch_StepCounter)."""
+        return int(self.a.BeatriceBatch_StepCounter(self.h))
 
     def convert(self, x):
         x = np.ascontiguousarray(x, np.float32)

@@ -702,6 +702,35 @@ int BeatriceHip_InjectTeamTimeoutPitch(Beatrice20rc0_PitchContext1* ctx) {
   *ctx->st.d_team_dead = 1;
   return 0;
 }
+// Test hook (beatrice_batch.h): a FRESH context's hop counter.  `seq` counts the calls enqueued (a pre-executed pitch hop included): 0 = no hop yet.
+int BeatriceHip_SetHopCount(int kind, void* ctx, int counter) {
+  if (!ctx || counter < 0 || counter >= B_HOP_WRAP) return -1;
+  if (kind == 1) {
+    auto* c = static_cast<Beatrice20rc0_PhoneContext1*>(ctx);
+    if (!c->ok || c->seq != 0) return -1;
+    c->hop_count = counter;
+  } else if (kind == 2) {
+    auto* c = static_cast<Beatrice20rc0_PitchContext1*>(ctx);
+    if (!c->ok) return -1;
+    std::lock_guard<std::mutex> own(c->spec_mu);
+    if (c->seq != 0) return -1;
+    c->hop_count = counter;
+  } else if (kind == 3) {
+    auto* c = static_cast<Beatrice20rc0_WaveformContext1*>(ctx);
+    if (!c->ok || c->seq != 0) return -1;
+    c->hop_count = counter;
+  } else {
+    return -1;
+  }
+  return 0;
+}
+int BeatriceHip_HopCount(int kind, const void* ctx) {
+  if (!ctx) return -1;
+  if (kind == 1) { auto* c = static_cast<const Beatrice20rc0_PhoneContext1*>(ctx); return c->ok ? c->hop_count : -1; }
+  if (kind == 2) { auto* c = static_cast<const Beatrice20rc0_PitchContext1*>(ctx); return c->ok ? c->hop_count : -1; }
+  if (kind == 3) { auto* c = static_cast<const Beatrice20rc0_WaveformContext1*>(ctx); return c->ok ? c->hop_count : -1; }
+  return -1;
+}
 
 // ================================ embedding setter =============================================
 // ref beatrice.h:309-311

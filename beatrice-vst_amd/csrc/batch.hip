@@ -1638,6 +1638,21 @@ int BeatriceBatch_InjectTeamTimeout(BeatriceBatch* b) {
   *b->wave.d_team_dead = 1;
   return 0;
 }
+// Test hook (beatrice_batch.h): a FRESH batch starts at another step counter -- the host mirror and the device's copy, as the tick-leave path
+// hands them to the in-order chain (tick_enable).  Nothing has been enqueued, so nothing is waited for.
+static_assert(BEATRICE_HIP_STEP_WRAP == B_HOP_WRAP, "beatrice_batch.h names the step counter's wrap");
+int BeatriceBatch_SetStepCounter(BeatriceBatch* b, int counter) {
+  BATCH_OPEN(b);
+  if (counter < 0 || counter >= B_HOP_WRAP) return -1;
+  if (b->steps_enqueued != 0 || b->tk.on || b->hs.on || b->r48.on || b->rb.on || b->io_slots > 0) return -1;
+  const int pair[2] = {counter, b->io_host};
+  if (!hip_ok(hipMemcpy(b->d_hop_next, pair, sizeof(pair), hipMemcpyHostToDevice), "step counter")) return -2;
+  b->hop_host = counter;
+  b->front_dirty = true;
+  for (bool& w : b->wave_dirty) w = true;
+  return 0;
+}
+int BeatriceBatch_StepCounter(const BeatriceBatch* b) { return b ? b->hop_host : -1; }
 int BeatriceBatch_Synchronize(BeatriceBatch* b) {
   BATCH_OPEN(b);
   return sync_all(b) ? 0 : -2;

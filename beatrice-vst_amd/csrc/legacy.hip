@@ -59,6 +59,7 @@ struct LPhoneCtx {
   hipStream_t stream = nullptr;
   float* h_io = nullptr;   // pinned: 160 in | mailbox (step counter) | 256 out
   int hop_count = 0;
+  bool hopped = false;     // a hop has run (BeatriceHip_SetHopCountLegacy: fresh contexts only)
   HopGraph graph;
   bool ok = false;
 };
@@ -68,6 +69,7 @@ struct LPitchCtx {
   hipStream_t stream = nullptr;
   float* h_io = nullptr;   // pinned: 160 in | mailbox (step counter, bin range) | 4 feat | 1 bin
   int hop_count = 0, min_q = 1, max_q = kLBins - 1;
+  bool hopped = false;
   void* own_sel[2] = {nullptr, nullptr};
   HopGraph graph;
   bool ok = false;
@@ -79,6 +81,7 @@ struct LWaveCtx {
   float* d_inputs = nullptr;   // device: 256 phone | 4 feat | 1 bin | step counter | 256 speaker vector
   float* h_io = nullptr;       // pinned: the same | 240 out
   int hop_count = 0;
+  bool hopped = false;
   HopGraph graph;
   bool ok = false;
 };
@@ -182,6 +185,7 @@ void extract_phone(const LPhoneModel* m, const float* input, float* output, LPho
   std::memcpy(h_in, input, sizeof(float) * B_IN_HOP);
   reinterpret_cast<int*>(h_in + B_IN_HOP)[0] = ctx->hop_count;
   ctx->hop_count = hop_next(ctx->hop_count);
+  ctx->hopped = true;
   bool ok = run_graph(ctx->graph, m->blob.d, ctx->stream, [&] {
     (void)hipMemcpyAsync(ctx->st.d_in, h_in, sizeof(float) * (B_IN_HOP + kMailboxWords), hipMemcpyHostToDevice, ctx->stream);
     phone_forward(m->w, ctx->st, ctx->stream);
@@ -204,6 +208,7 @@ void estimate_pitch(const LPitchModel* m, const float* input, int* out_q, float*
   int* mb = reinterpret_cast<int*>(h_in + B_IN_HOP);
   mb[0] = ctx->hop_count; mb[1] = ctx->min_q; mb[2] = ctx->max_q;
   ctx->hop_count = hop_next(ctx->hop_count);
+  ctx->hopped = true;
   bool ok = run_graph(ctx->graph, m->blob.d, ctx->stream, [&] {
     (void)hipMemcpyAsync(ctx->st.d_in, h_in, sizeof(float) * (B_IN_HOP + kMailboxWords), hipMemcpyHostToDevice, ctx->stream);
     pitch_forward(m->w, ctx->st, ctx->stream);
@@ -232,6 +237,7 @@ void generate_waveform(const LWaveModel* m, const float* phone, const int* q, co
   std::memcpy(h_in + kLPhoneCh + 5, &ctx->hop_count, sizeof(int));
   std::memcpy(h_in + kLPhoneCh + 6, speaker, sizeof(float) * B_HID);
   ctx->hop_count = hop_next(ctx->hop_count);
+  ctx->hopped = true;
   bool ok = run_graph(ctx->graph, m->blob.d, ctx->stream, [&] {
     (void)hipMemcpyAsync(ctx->d_inputs, h_in, sizeof(float) * kWaveInFloats, hipMemcpyHostToDevice, ctx->stream);
     wave_forward(m->w, ctx->st, ctx->stream);
@@ -270,6 +276,26 @@ Beatrice_ErrorCode read_rows(const char* path, float* output) {
 }
 
 }  // namespace
+
+// Test hook (beatrice_batch.h): a FRESH legacy context's hop counter; the contexts of both generations are the shared structs above
+// under their own names (below), so one entry point serves both.
+extern "C" int BeatriceHip_SetHopCountLegacy(int kind, void* ctx, int counter) {
+  if (!ctx || counter < 0 || counter >= B_HOP_WRAP) return -1;
+  auto set = [counter](auto* c) { if (!c->ok || c->hopped) return -1; c->hop_count = counter; return 0; };
+  if (kind == 1) return set(reinterpret_cast<LPhoneCtx*>(ctx));
+  if (kind == 2) return set(reinterpret_cast<LPitchCtx*>(ctx));
+  if (kind == 3) return set(reinterpret_cast<LWaveCtx*>(ctx));
+  return -1;
+}
+
+extern "C" int BeatriceHip_HopCountLegacy(int kind, const void* ctx) {
+  if (!ctx) return -1;
+  auto get = [](const auto* c) { return c->ok ? c->hop_count : -1; };
+  if (kind == 1) return get(reinterpret_cast<const LPhoneCtx*>(ctx));
+  if (kind == 2) return get(reinterpret_cast<const LPitchCtx*>(ctx));
+  if (kind == 3) return get(reinterpret_cast<const LWaveCtx*>(ctx));
+  return -1;
+}
 
 // the opaque objects of one generation are the shared ones under its own type names
 #define BEATRICE_LEGACY_GENERATION(G)                                                                                                  \

@@ -56,6 +56,17 @@ int BeatriceHip_InjectTeamTimeout(Beatrice20rc0_WaveformContext1* ctx);
  * steps since the last BeatriceBatch_Synchronize are void: it returns -2 once, the stream restarts from silence, the batch stays usable).  -1: no team launch. */
 int BeatriceHip_InjectTeamTimeoutPhone(Beatrice20rc0_PhoneContext1* ctx);
 int BeatriceHip_InjectTeamTimeoutPitch(Beatrice20rc0_PitchContext1* ctx);
+/* Test hook: the hop counter of a 1-stream context (the same counter, the same wrap at BEATRICE_HIP_STEP_WRAP, below: it addresses the
+ * context's rings and travels to the device with every hop's input).  kind: 1 phone, 2 pitch, 3 waveform context; ctx a context of the
+ * 2.0.0-rc.0 generation (BeatriceHip_SetHopCount) or of a legacy generation, Beatrice20a2_* / Beatrice20b1_* (BeatriceHip_SetHopCountLegacy).
+ * FRESH contexts only -- before the context's first hop, when all its rings are zeros and a context started at counter c computes what one
+ * started at 0 computes.  The three contexts of a stream count independently: set all three.  0; -1 and no change for an unknown kind, a
+ * bad context, a counter outside [0, BEATRICE_HIP_STEP_WRAP) or a context that has run a hop.  BeatriceHip_HopCount[Legacy] reads the
+ * counter of the context's NEXT hop (-1: unknown kind, bad context). */
+int BeatriceHip_SetHopCount(int kind, void* ctx, int counter);
+int BeatriceHip_SetHopCountLegacy(int kind, void* ctx, int counter);
+int BeatriceHip_HopCount(int kind, const void* ctx);
+int BeatriceHip_HopCountLegacy(int kind, const void* ctx);
 /* The pitch call beside the phone call.  The reference's hop calls ExtractPhone1 and EstimatePitch1 one after the other on the SAME 160 samples
  * (src/common/processor_core_2.cc:184,188); the two modules are independent.  Once a pitch context has been called right after a phone context with
  * the same samples (same thread), that phone context's calls also start the pitch context's hop for their input on the pitch context's own stream;
@@ -182,6 +193,17 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
 void BeatriceBatch_Destroy(BeatriceBatch* b);
 int BeatriceBatch_IsHealthy(const BeatriceBatch* b);
 int BeatriceBatch_InjectTeamTimeout(BeatriceBatch* b);   /* test hook, see BeatriceHip_InjectTeamTimeout */
+/* Test hook: where the step counter starts.  Every activation ring is addressed by (step counter mod its slot count); the counter -- on the
+ * device and in the host's mirror -- wraps to 0 after BEATRICE_HIP_STEP_WRAP - 1 (lcm(1..17): every slot count divides it; 34 hours of 10 ms
+ * steps), and a test cannot feed twelve million steps to get there.  BeatriceBatch_SetStepCounter sets the host mirror and the device's
+ * copy on a FRESH batch only: one that has not taken a step yet, has no binding (resident I/O, 48 kHz or any-rate blocks, host streaming)
+ * and is outside tick mode.  The rings of a fresh batch are all zeros, so a batch started at counter c computes exactly what one started
+ * at 0 computes -- only the slots its history lands in differ (tests/test_gpu_counter_wrap.py).  -1 and no change: a counter outside
+ * [0, BEATRICE_HIP_STEP_WRAP), a batch that has taken a step, a binding, tick mode.  It adds nothing to any step and is not a mode entry
+ * point (no row in the MODES table).  BeatriceBatch_StepCounter returns the host mirror: the counter of the NEXT step (-1: no batch). */
+#define BEATRICE_HIP_STEP_WRAP 12252240
+int BeatriceBatch_SetStepCounter(BeatriceBatch* b, int counter);
+int BeatriceBatch_StepCounter(const BeatriceBatch* b);
 int BeatriceBatch_NumStreams(const BeatriceBatch* b);
 int BeatriceBatch_HopsPerStep(const BeatriceBatch* b);
 /* bytes of per-stream activation history (all rings of all three modules) held for the n_streams streams */

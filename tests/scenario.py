@@ -632,15 +632,17 @@ def run_in_order(env, scn):
     return out, q, bins
 
 
-def run_product(env, scn):
+def run_product(env, scn, start_counter=None):
     """([steps][B][H * 240], raw pitch bins [B] of the last hop) from ONE batch of H hops per step walked through the scenario's phases,
-    state carried from phase to phase.  Every mode-changing call is asserted to return 0."""
+    state carried from phase to phase.  Every mode-changing call is asserted to return 0.  start_counter: the new batch's step counter
+    (BeatriceBatch_SetStepCounter; the counter wraps at bv.STEP_WRAP) -- a fresh batch computes the same samples wherever it starts, so
+    the in-order reference and the oracle know nothing of it; the run must then end at (start_counter + steps) mod the wrap."""
     from tick_driver import Resident
     bv, B, H = env.bv, scn["B"], scn["H"]
     at, starts = _phase_table(scn["phases"])
     x = inputs(bv, scn)
     m = bv.Models(env.product, env.model_dir)
-    batch = bv.Batch(m, B, hops_per_step=H)
+    batch = bv.Batch(m, B, hops_per_step=H, start_counter=start_counter)
     a, h = batch.a, batch.h
     out = np.zeros((len(at), B, H * 240), np.float32)
 
@@ -702,17 +704,29 @@ def run_product(env, scn):
                 assert done == k0 + n
                 assert a.BeatriceBatch_EnableHostStreaming(h, 0) == 0
         q = batch.intermediates()[1].reshape(B, H)[:, H - 1].copy()
+        if start_counter is not None:
+            end = batch.step_counter()
+            print("%s: step counter %d before, %d after %d steps" % (scenario_id(scn), start_counter, end, len(at)))
+            assert end == (start_counter + len(at)) % bv.STEP_WRAP
     finally:
         batch.close()
         m.close()
     return out, q
 
 
-def compare(env, scn, say=print):
-    """The comparison of tests/test_gpu_scenarios.py for one scenario; returns the list of failures (strings, empty = fine)."""
-    got, q = run_product(env, scn)
-    ref, ref_q, bins = run_in_order(env, scn)
-    want = run_oracle(env, scn, scn["sample"])
+def compare(env, scn, say=print, start_counter=None, references=None):
+    """The comparison of tests/test_gpu_scenarios.py for one scenario; returns the list of failures (strings, empty = fine).
+    start_counter: see run_product (the product through the phases only).  references: a dict in which the scenario's in-order and oracle
+    legs are kept for a second comparison of the same scenario."""
+    got, q = run_product(env, scn, start_counter)
+    key = scenario_id(scn)
+    if references is None or key not in references:
+        legs = run_in_order(env, scn) + (run_oracle(env, scn, scn["sample"]),)
+        if references is not None:
+            references[key] = legs
+    else:
+        legs = references[key]
+    ref, ref_q, bins, want = legs
     steps, B = got.shape[0], scn["B"]
     present = [[s not in scn["absent"][k] for s in range(B)] for k in range(steps)]
     stay = never_absent(scn)
@@ -748,6 +762,8 @@ def main(argv=None):
     ap.add_argument("--phases", help="e.g. D:40,A:6 (default: as in the committed list for that seed)")
     ap.add_argument("--dump", help="write the scenario as json")
     ap.add_argument("--gpu", action="store_true", help="run the product against its in-order chain and the oracle")
+    ap.add_argument("--start-counter", type=int, help="with --gpu: the step counter the product's batch starts at (it wraps at 12 252 240; the in-order "
+                    "chain and the oracle ignore it), e.g. 12252240 minus half the scenario's steps")
     args = ap.parse_args(argv)
     listed = {s[0]: s for s in SEEDS}.get(args.seed)
     B = args.B or (listed[1] if listed else 5)
@@ -778,7 +794,7 @@ def main(argv=None):
         with tempfile.TemporaryDirectory() as d:
             make_model.make_model(d, n_speakers=N_SPEAKERS)
             env = Env(bv, bv.Abi(os.path.join(root, "oracle", "libbeatrice_oracle.so")), bv.load_product(), d)
-            problems = compare(env, scn)
+            problems = compare(env, scn, start_counter=args.start_counter)
         for p in problems:
             print(p)
         return 1 if problems else 0
