@@ -470,6 +470,12 @@ _BATCH = {
     "BeatriceBatch_MaxWrapperBlock": (C.c_int, [_vp]),
     "BeatriceBatch_ConfigureWrapperRates": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "BeatriceBatch_ProcessBlocksRagged": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "BeatriceBatch_SetStreamRate": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "BeatriceBatch_RestartStreamWrapper": (C.c_int, [_vp, C.c_int]),
+    "BeatriceBatch_StreamRate": (C.c_double, [_vp, C.c_int]),
+    "BeatriceBatch_WrapperBlobBytes": (C.c_size_t, [_vp]),
+    "BeatriceBatch_ExportStreamWrappers": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
+    "BeatriceBatch_ImportStreamWrappers": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
     "BeatriceBatch_Synchronize": (C.c_int, [_vp]),
     "BeatriceBatch_BindResidentIO": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "BeatriceBatch_SetStream": (C.c_int, [_vp, _vp]),
@@ -618,6 +624,42 @@ class Batch:
         buf = C.create_string_buffer(bytes(blobs), max(1, len(blobs)))
         self._check(self.a.BeatriceBatch_ImportStreams(self.h, len(idx), iptr(idx), C.cast(buf, _vp),
                                                        None if em is None else iptr(em), 0 if em is None else len(em)))
+
+    def set_stream_rate(self, stream, rate):
+        """One stream's SetSampleRate (BeatriceBatch_SetStreamRate): its resampler pair and FIFO restart at `rate`, its gains keep
+        their state; an equal rate does nothing.  No other stream changes."""
+        self._check(self.a.BeatriceBatch_SetStreamRate(self.h, int(stream), float(rate)))
+
+    def restart_stream_wrapper(self, stream):
+        """The same restart at the stream's present rate (BeatriceBatch_RestartStreamWrapper); with BeatriceBatch_ResetStream it
+        turns the slot over to a new caller."""
+        self._check(self.a.BeatriceBatch_RestartStreamWrapper(self.h, int(stream)))
+
+    def stream_rate(self, stream):
+        """The stream's host rate (0.0 on a batch without clocks per stream)."""
+        return float(self.a.BeatriceBatch_StreamRate(self.h, int(stream)))
+
+    def wrapper_blob_bytes(self):
+        """Bytes of one stream's wrapper blob (0 where export_stream_wrappers / import_stream_wrappers are refused)."""
+        return int(self.a.BeatriceBatch_WrapperBlobBytes(self.h))
+
+    def export_stream_wrappers(self, streams):
+        """The any-rate wrapper's state of `streams` -- rate, resampler clocks, FIFO, gain clocks, filter histories -- as
+        len(streams) wrapper blobs back to back (BeatriceBatch_ExportStreamWrappers).  Drains; changes nothing."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        size = self.wrapper_blob_bytes()
+        buf = C.create_string_buffer(max(1, len(idx) * size))
+        self._check(self.a.BeatriceBatch_ExportStreamWrappers(self.h, len(idx), iptr(idx), C.cast(buf, _vp)))
+        return buf.raw[:len(idx) * size]
+
+    def import_stream_wrappers(self, streams, blobs):
+        """Wrapper blob i of `blobs` becomes the wrapper state of stream streams[i] (BeatriceBatch_ImportStreamWrappers); a rate
+        this batch has no class for gets one."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if len(blobs) != len(idx) * self.wrapper_blob_bytes():
+            raise ValueError("import_stream_wrappers: %d bytes for %d streams of %d bytes each" % (len(blobs), len(idx), self.wrapper_blob_bytes()))
+        buf = C.create_string_buffer(bytes(blobs), max(1, len(blobs)))
+        self._check(self.a.BeatriceBatch_ImportStreamWrappers(self.h, len(idx), iptr(idx), C.cast(buf, _vp)))
 
     def close(self):
         if self.h:

@@ -27,6 +27,7 @@
 #include "stream_blob.h"
 #include "tick.hip.h"
 #include "wrapper.hip.h"
+#include "wrapper_blob.h"
 
 using namespace bhip;
 
@@ -277,6 +278,12 @@ struct BeatriceBatch {
     StagedRing<wrapn::RagStream> rs;               // [kStage][B]: a call's per-stream records, pinned staging and device copy
     long long calls = 0;
     DevBuf<unsigned char> d_frozen;                // [kMaxChunks][B]: per FIFO chunk, the streams that do not fire a hop in it
+    // BeatriceBatch_ExportStreamWrappers / ImportStreamWrappers (wrapper_blob.h): the one-piece table over d_wrap for stream_gather /
+    // stream_scatter and the staging pair -- `blob_cap` = min(n, 16) blobs each -- made by the first call that needs them
+    DevBuf<BlobPiece> d_blob_piece;
+    PinnedBuf<unsigned char> h_blob_stage;
+    DevBuf<unsigned char> d_blob_stage;
+    int blob_cap = 0;
   } rw;
   // The any-rate wrapper around the tick pipeline (BeatriceBatch_BindResidentBlocks): host-rate blocks resident on the device,
   // the input half of the chain in front of the ticks, the output half `delay` calls later (wrapper.hip.h wrap_post_kernel)

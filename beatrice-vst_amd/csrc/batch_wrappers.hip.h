@@ -482,6 +482,194 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
   return ok ? 0 : -2;
 }
 
+// ---- one stream's host side on its own: its rate, its restart, its wrapper blob (beatrice_batch.h; the blob: wrapper_blob.h) -------
+// Where BeatriceBatch_ProcessBlocksRagged is allowed -- in order, one hop per step, after BeatriceBatch_ConfigureWrapperRates, no
+// binding -- a stream's rate, clocks, gain clocks and StreamState can be set, restarted and moved without touching another stream.
+// Everything that can be refused or can fail is done before anything is committed: the new class tables are built and uploaded into a
+// buffer of their own first, the device state is written next, the host's bookkeeping last.
+namespace {
+static_assert(sizeof(wrapn::StreamState) == wblob::kStateBytes && wblob::kFifo == wrapn::kBlock, "wrapper_blob.h restates the wrapper's state block");
+bool rag_settings_allowed(const BeatriceBatch* b) { return modes::allowed(Entry::ProcessBlocksRagged, flags_of(b)); }
+// The batch's rate classes once every stream s runs at want[s]: the old classes still in use keep their order, the rates no stream has
+// had yet (`fresh`, configured by the caller) follow; classes no stream uses any more are gone.  Unchanged set: nothing is built.
+struct RagTables {
+  bool rebuilt = false;
+  std::vector<wrapn::WrapPlan> classes;
+  std::vector<int> cls, taps_down_off, taps_up_off;
+  DevBuf<float> d_taps;
+};
+bool rag_retable(const BeatriceBatch* b, const std::vector<double>& want, const std::vector<wrapn::WrapPlan>& fresh, RagTables& t) {
+  const BeatriceBatch::RaggedWrap& r = b->rw;
+  const int B = b->B;
+  auto used = [&](double rate) { for (int s = 0; s < B; ++s) if (want[s] == rate) return true; return false; };
+  for (const wrapn::WrapPlan& p : r.classes) if (used(p.rate)) t.classes.push_back(p);
+  t.rebuilt = t.classes.size() != r.classes.size();
+  for (const wrapn::WrapPlan& p : fresh) {
+    bool have = false;
+    for (const wrapn::WrapPlan& q : t.classes) have = have || q.rate == p.rate;
+    if (!have && used(p.rate)) { t.classes.push_back(p); t.rebuilt = true; }
+  }
+  t.cls.assign(B, -1);
+  for (int s = 0; s < B; ++s)
+    for (size_t i = 0; i < t.classes.size(); ++i) if (t.classes[i].rate == want[s]) { t.cls[s] = (int)i; break; }
+  for (int s = 0; s < B; ++s) if (t.cls[s] < 0) return false;   // (cannot be: every rate wanted is an old class's or a fresh one's)
+  if (!t.rebuilt) return true;
+  std::vector<float> taps;
+  for (const wrapn::WrapPlan& p : t.classes) {
+    t.taps_down_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_down.begin(), p.taps_down.end());
+    t.taps_up_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_up.begin(), p.taps_up.end());
+  }
+  return t.d_taps.alloc(taps.size(), "ragged taps", false) &&
+         hip_ok(hipMemcpy(t.d_taps, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice), "ragged taps up");
+}
+// (after a drain: no launch reads the old table any more)
+void rag_commit(BeatriceBatch* b, RagTables& t) {
+  BeatriceBatch::RaggedWrap& r = b->rw;
+  if (t.rebuilt) {
+    r.d_taps = std::move(t.d_taps); r.taps_down_off = std::move(t.taps_down_off); r.taps_up_off = std::move(t.taps_up_off);
+    r.classes = std::move(t.classes);
+  }
+  r.cls = std::move(t.cls);
+}
+void rag_rates(const BeatriceBatch* b, std::vector<double>& rates) {
+  rates.resize(b->B);
+  for (int s = 0; s < b->B; ++s) rates[s] = b->rw.classes[b->rw.cls[s]].rate;
+}
+// the class of `rate` among the batch's and those configured so far for this call; a rate none has had is configured (nullptr: refused)
+const wrapn::WrapPlan* rag_class_of(const BeatriceBatch* b, double rate, std::vector<wrapn::WrapPlan>& fresh) {
+  if (!std::isfinite(rate)) return nullptr;
+  for (const wrapn::WrapPlan& p : b->rw.classes) if (p.rate == rate) return &p;
+  for (const wrapn::WrapPlan& p : fresh) if (p.rate == rate) return &p;
+  wrapn::WrapPlan p;
+  if (!p.configure(rate)) return nullptr;
+  fresh.push_back(p);
+  return &fresh.back();
+}
+// reference SetSampleRate for ONE stream (processor_core_2.cc:421-429): resampler pair and FIFO start over at `rate`, the gains keep
+// their state and ramp at the new rate from the next block on
+int rag_restart(BeatriceBatch* b, int s, double rate) {
+  BeatriceBatch::RaggedWrap& r = b->rw;
+  std::vector<wrapn::WrapPlan> fresh;
+  if (!rag_class_of(b, rate, fresh)) return -1;
+  std::vector<double> want;
+  rag_rates(b, want);
+  want[s] = rate;
+  RagTables t;
+  if (!rag_retable(b, want, fresh, t) || !sync_all(b)) return -2;
+  if (!hip_ok(hipMemsetAsync(b->d_wrap + s, 0, sizeof(wrapn::StreamState), b->stream), "stream wrapper state0") ||
+      !hip_ok(hipStreamSynchronize(b->stream), "stream wrapper sync"))
+    return -2;
+  rag_commit(b, t);
+  const int hi = r.classes[r.cls[s]].hi;
+  r.clk[s] = BeatriceBatch::RaggedWrap::Clock{hi - 1, hi - 1, 0};
+  b->wrap_gains_constant = false;
+  return 0;
+}
+// the piece table of the wrapper blobs (once per batch) and staging for min(n, 16) of them
+bool wblob_prepare(BeatriceBatch* b, int n) {
+  BeatriceBatch::RaggedWrap& r = b->rw;
+  if (!r.d_blob_piece) {
+    const unsigned words = (unsigned)(sizeof(wrapn::StreamState) / sizeof(float));
+    const BlobPiece piece{reinterpret_cast<float*>(b->d_wrap.get()), words, words, 1, (unsigned long long)(wblob::kOffState / sizeof(float))};
+    DevBuf<BlobPiece> d_piece;
+    if (!d_piece.alloc(1, "wrapper blob piece", false) || !hip_ok(hipMemcpy(d_piece, &piece, sizeof(piece), hipMemcpyHostToDevice), "wrapper blob piece up")) return false;
+    r.d_blob_piece = std::move(d_piece);
+  }
+  const int want = std::min(n, sblob::kMaxRound);
+  if (r.blob_cap < want) {
+    PinnedBuf<unsigned char> h_stage;
+    DevBuf<unsigned char> d_stage;
+    if (!h_stage.alloc((size_t)want * wblob::kBlobBytes, "wrapper blob staging", false) || !d_stage.alloc((size_t)want * wblob::kBlobBytes, "wrapper blob staging")) return false;
+    r.h_blob_stage = std::move(h_stage); r.d_blob_stage = std::move(d_stage); r.blob_cap = want;
+  }
+  return true;
+}
+}  // namespace
+
+int BeatriceBatch_SetStreamRate(BeatriceBatch* b, int stream, double host_sample_rate) {
+  BATCH_OPEN(b);
+  if (!rag_settings_allowed(b) || stream < 0 || stream >= b->B) return -1;
+  if (b->rw.classes[b->rw.cls[stream]].rate == host_sample_rate) return 0;   // (the reference's SetSampleRate: an equal rate is no call at all)
+  return rag_restart(b, stream, host_sample_rate);
+}
+int BeatriceBatch_RestartStreamWrapper(BeatriceBatch* b, int stream) {
+  BATCH_OPEN(b);
+  if (!rag_settings_allowed(b) || stream < 0 || stream >= b->B) return -1;
+  return rag_restart(b, stream, b->rw.classes[b->rw.cls[stream]].rate);
+}
+double BeatriceBatch_StreamRate(const BeatriceBatch* b, int stream) {
+  if (!b || !b->ok || !rag_settings_allowed(b) || stream < 0 || stream >= b->B) return 0.0;
+  return b->rw.classes[b->rw.cls[stream]].rate;
+}
+size_t BeatriceBatch_WrapperBlobBytes(const BeatriceBatch* b) { return b && b->ok && rag_settings_allowed(b) ? wblob::kBlobBytes : 0; }
+
+int BeatriceBatch_ExportStreamWrappers(BeatriceBatch* b, int n, const int* streams, void* blobs) {
+  BATCH_OPEN(b);
+  if (!rag_settings_allowed(b) || !blob_streams_ok(b, n, streams) || !blobs) return -1;
+  if (!wblob_prepare(b, n) || !sync_all(b)) return -2;
+  BeatriceBatch::RaggedWrap& r = b->rw;
+  unsigned char* out = static_cast<unsigned char*>(blobs);
+  for (int at = 0; at < n; at += r.blob_cap) {
+    BlobRound round{};
+    round.n = std::min(r.blob_cap, n - at);
+    for (int j = 0; j < round.n; ++j) round.streams[j] = streams[at + j];
+    if (!stream_gather(r.d_blob_piece, 1, round, reinterpret_cast<float*>(r.d_blob_stage.get()), wblob::kBlobBytes / sizeof(float), b->stream) ||
+        !hip_ok(hipMemcpyAsync(r.h_blob_stage, r.d_blob_stage, (size_t)round.n * wblob::kBlobBytes, hipMemcpyDeviceToHost, b->stream), "wrapper blobs down") ||
+        !hip_ok(hipStreamSynchronize(b->stream), "wrapper gather"))
+      return -2;
+    for (int j = 0; j < round.n; ++j) {
+      const int s = round.streams[j];
+      unsigned char* blob = r.h_blob_stage + (size_t)j * wblob::kBlobBytes;
+      const BeatriceBatch::RaggedWrap::Clock& c = r.clk[s];
+      wblob::write_header(r.classes[r.cls[s]].rate, c.phase_down, c.phase_up, c.fill, b->gain_in[s].target_db, b->gain_in[s].now_db,
+                          b->gain_out[s].target_db, b->gain_out[s].now_db, blob);
+      std::memcpy(out + (size_t)(at + j) * wblob::kBlobBytes, blob, wblob::kBlobBytes);
+    }
+  }
+  return 0;
+}
+
+int BeatriceBatch_ImportStreamWrappers(BeatriceBatch* b, int n, const int* streams, const void* blobs) {
+  BATCH_OPEN(b);
+  if (!rag_settings_allowed(b) || !blob_streams_ok(b, n, streams) || !blobs) return -1;
+  BeatriceBatch::RaggedWrap& r = b->rw;
+  const unsigned char* in = static_cast<const unsigned char*>(blobs);
+  std::vector<wblob::Header> taken(n);
+  std::vector<wrapn::WrapPlan> fresh;
+  std::vector<double> want;
+  rag_rates(b, want);
+  for (int i = 0; i < n; ++i) {   // every blob is looked at before anything is drained, built, uploaded or written
+    const unsigned char* blob = in + (size_t)i * wblob::kBlobBytes;
+    double rate = 0.0;
+    if (wblob::read_rate(blob, wblob::kBlobBytes, &rate) != wblob::kOk) return -1;
+    const wrapn::WrapPlan* p = rag_class_of(b, rate, fresh);   // (the rate through WrapPlan::configure: its hi bounds the clocks)
+    if (!p || wblob::validate(blob, wblob::kBlobBytes, p->hi, &taken[i]) != wblob::kOk) return -1;
+    want[streams[i]] = rate;
+  }
+  RagTables t;
+  if (!rag_retable(b, want, fresh, t) || !wblob_prepare(b, n) || !sync_all(b)) return -2;
+  for (int at = 0; at < n; at += r.blob_cap) {
+    BlobRound round{};
+    round.n = std::min(r.blob_cap, n - at);
+    for (int j = 0; j < round.n; ++j) round.streams[j] = streams[at + j];
+    std::memcpy(r.h_blob_stage, in + (size_t)at * wblob::kBlobBytes, (size_t)round.n * wblob::kBlobBytes);
+    if (!hip_ok(hipMemcpyAsync(r.d_blob_stage, r.h_blob_stage, (size_t)round.n * wblob::kBlobBytes, hipMemcpyHostToDevice, b->stream), "wrapper blobs up") ||
+        !stream_scatter(r.d_blob_piece, 1, round, reinterpret_cast<const float*>(r.d_blob_stage.get()), wblob::kBlobBytes / sizeof(float), b->stream) ||
+        !hip_ok(hipStreamSynchronize(b->stream), "wrapper scatter"))
+      return -2;
+  }
+  rag_commit(b, t);
+  for (int i = 0; i < n; ++i) {
+    const int s = streams[i];
+    const wblob::Header& h = taken[i];
+    r.clk[s] = BeatriceBatch::RaggedWrap::Clock{h.phase_down, h.phase_up, h.fill};
+    b->gain_in[s].target_db = h.in_target_db; b->gain_in[s].now_db = h.in_now_db;
+    b->gain_out[s].target_db = h.out_target_db; b->gain_out[s].now_db = h.out_now_db;
+  }
+  b->wrap_gains_constant = false;
+  return 0;
+}
+
 // ---- the same wrapper around the TICK pipeline (throughput form, resident blocks) ------------------------------------------------
 // One call = one host-rate block per stream from slot `call mod n_slots` of d_in: gains and the first resampling direction, the
 // 480-sample accumulation, a model hop into the tick pipeline every time it fills (one tick per hop, at least one tick per

@@ -186,7 +186,7 @@ def affine_speaker(rank, world, local_stream, n_speakers):
     return rank + world * (local_stream % mine)
 
 
-def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None, reset_source=False):
+def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None, reset_source=False, with_wrapper=False):
     """Stream src_streams[i] of src_batch goes on as stream dst_streams[i] of dst_batch, with its state and settings
     (Batch.export_streams / Batch.import_streams): its next step there is bit for bit the step it would have run in
     src_batch.  Both batches drain.  The two are batches of ONE process (any two GPUs of it: each call runs on its batch's
@@ -195,16 +195,26 @@ def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None,
     weights, are equal there is the caller's promise.  reset_source: BeatriceBatch_ResetStream on the source streams
     afterwards, so that the slots start from silence for their next users.  Returns the blobs.
 
+    with_wrapper: both batches run clocks per stream (BeatriceBatch_ConfigureWrapperRates / ProcessBlocksRagged) and the stream
+    takes its host side along as well -- its rate, resampler histories and clocks, FIFO and gain ramps (Batch.export_stream_wrappers /
+    Batch.import_stream_wrappers) -- so that its next BLOCK there is the block it would have got in src_batch; reset_source then
+    also restarts the source slots' wrappers.  Returns (blobs, wrapper_blobs).
+
     Between ranks the blob is plain bytes: export_streams on the rank that has the stream, broadcast_bytes (or a
     point-to-point send of a uint8 tensor) to the rank that takes it, import_streams there."""
     if len(src_streams) != len(dst_streams):
         raise ValueError("move_streams: %d source streams, %d destination streams" % (len(src_streams), len(dst_streams)))
     blobs = src_batch.export_streams(src_streams)
+    wrapper_blobs = src_batch.export_stream_wrappers(src_streams) if with_wrapper else None
     dst_batch.import_streams(dst_streams, blobs, entry_map)
+    if with_wrapper:
+        dst_batch.import_stream_wrappers(dst_streams, wrapper_blobs)
     if reset_source:
         for s in src_streams:
             src_batch._check(src_batch.a.BeatriceBatch_ResetStream(src_batch.h, int(s)))
-    return blobs
+            if with_wrapper:
+                src_batch.restart_stream_wrapper(s)
+    return (blobs, wrapper_blobs) if with_wrapper else blobs
 
 
 def max_over_ranks(value, world, dist, torch, device):

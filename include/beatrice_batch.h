@@ -171,6 +171,9 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *   (7) a rule enabled in D / F stays on when the batch leaves tick mode after BeatriceBatch_ConfigureWrapperRates (which keeps the rule's buffers): while it is on,
  *       these calls are refused in C (and a second EnableTickPipeline(1) in D), and EnableSilentBlockRule(1) returns 0.  EnableSilentBlockRule(0) clears it.
  *   (8) H = 1 / 2 / 4: -1 on a batch of eight hops per step.
+ *   (9) not rows of this table, because they are settings: BeatriceBatch_SetStreamRate, RestartStreamWrapper, StreamRate, WrapperBlobBytes,
+ *       ExportStreamWrappers and ImportStreamWrappers work exactly where the row "ProcessBlocksRagged" says ok -- A and S, one hop per step,
+ *       once BeatriceBatch_ConfigureWrapperRates has been called, nothing bound -- and are refused (-1, 0.0 or 0; nothing changes) everywhere else.
  *
  * Environment variables the library reads: BEATRICE_HIP_DEBUG (print HIP errors to stderr), BEATRICE_HIP_CUMASK ("lo-hi;lo-hi;..": CU masks
  * of the stage-pipelining streams), BEATRICE_HIP_HOP_GRAPH (the 1-stream calls replayed as hipGraphs), BEATRICE_HIP_NO_SPECULATION (no pitch hop beside
@@ -348,7 +351,8 @@ long long BeatriceBatch_TicksLaunched(const BeatriceBatch* b);
  * pitch parameters, and the stream's codebook-lottery engine, which continues its sequence.  A header names the hops per step, the source
  * batch's step counter and the layout of every ring.  NOT in a blob, because it belongs to the slot and BeatriceBatch_ResetStream does
  * not restart it either: the any-rate wrapper's per-stream state (BeatriceBatch_ProcessBlocks*, BeatriceBatch_BindResidentBlocks*: the
- * resampler histories, the 480-sample FIFO, the gain clocks, the per-stream rate clocks).
+ * resampler histories, the 480-sample FIFO, the gain clocks, the per-stream rate clocks).  For a batch with clocks per stream that state
+ * travels as a second token of its own: BeatriceBatch_ExportStreamWrappers / BeatriceBatch_ImportStreamWrappers, below.
  * A blob is a short-lived token between two batches of the SAME library build with the same hops per step, not a storage format:
  * BeatriceBatch_ImportStreams refuses whatever it does not recognise and attempts no compatibility.  Between processes it is plain bytes.
  * Both calls work in every mode and are settings, not mode entry points (no row in the MODES table).  Both drain as
@@ -454,6 +458,44 @@ int BeatriceBatch_MaxWrapperBlock(const BeatriceBatch* b);
  * move, its output block is zeros.  In-order mode.  Bit-identical to one reference wrapper per stream. */
 int BeatriceBatch_ConfigureWrapperRates(BeatriceBatch* b, const double* rates);
 int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* out, int channels, const int* n_samples, int apply_silent_rule);
+/* ONE stream's host side of such a batch, without touching the others: a caller changes its sample rate, a slot goes to a new caller, a
+ * stream moves to another batch with its resampler histories, FIFO, clocks and gain ramps.  All six calls below work where
+ * BeatriceBatch_ProcessBlocksRagged works (MODES, footnote 9: in order or with the in-order silent rule, one hop per step, after
+ * BeatriceBatch_ConfigureWrapperRates, no binding) and are refused with -1 (the getters: 0.0 / 0) everywhere else, changing nothing: before
+ * BeatriceBatch_ConfigureWrapperRates, under the uniform BeatriceBatch_ConfigureWrapper alone, in modes B - G and P.  They are settings,
+ * not mode entry points (no row in the MODES table); a call that is not refused first waits for what the batch has enqueued.
+ * BeatriceBatch_SetStreamRate is the reference's SetSampleRate (processor_core_2.cc:421-429) for that one stream: an equal rate returns 0
+ * and does nothing; otherwise the stream's two resampler histories and its FIFO become zeros, its two clocks and its FIFO fill start
+ * over, and its gains keep their target and present value and ramp at the new rate from the next block on.  The stream's model state and
+ * settings are untouched, and no bit of any other stream changes -- device state, clocks, gains.  BeatriceBatch_RestartStreamWrapper is
+ * the same restart at the stream's present rate (the reference: SetSampleRate(another rate), SetSampleRate(the rate)); together with
+ * BeatriceBatch_ResetStream it turns a slot over to a new caller.  BeatriceBatch_StreamRate: the stream's rate (0.0: none / bad argument).
+ * Streams of equal rate share their tap tables (a rate class).  A rate no stream has had becomes a new class; the tables are rebuilt
+ * whenever the set of rates in use changes, without the classes no stream uses any more, so a batch never holds more classes than
+ * streams; every other stream goes on reading the same taps.
+ * -1 and no change: a stream out of range; a rate that is not finite, <= 0, or whose filter history exceeds the state block (above
+ * 384 kHz).  -2: HIP or allocation failure -- the new tables are built before anything is committed, so host and device state of every
+ * stream still agree. */
+int BeatriceBatch_SetStreamRate(BeatriceBatch* b, int stream, double host_sample_rate);
+int BeatriceBatch_RestartStreamWrapper(BeatriceBatch* b, int stream);
+double BeatriceBatch_StreamRate(const BeatriceBatch* b, int stream);
+/* The wrapper's per-stream state as a token of its own, beside the stream blob of BeatriceBatch_ExportStreams: the stream's rate, its
+ * two resampler clocks and FIFO fill, both gain clocks (target and present gain in dB), its four filter histories and the 480-sample
+ * FIFO.  After BeatriceBatch_ExportStreamWrappers(X, s) and BeatriceBatch_ImportStreamWrappers(Y, t) -- and the stream blob's pair, in
+ * either order: the two tokens are independent -- the next block of stream t through BeatriceBatch_ProcessBlocksRagged on Y is bit for
+ * bit the block stream s would have got from X, whatever the block lengths that follow.  Export changes nothing in X; import changes no
+ * other stream of Y and adds the rate's class if Y lacks it (as BeatriceBatch_SetStreamRate does).  One launch per 16 streams each way.
+ * Like the stream blob it is a short-lived token between two batches of the SAME library build, not a storage format
+ * (beatrice-vst_amd/csrc/wrapper_blob.h: what is refused, and why every blob that is taken keeps the kernels inside their buffers).
+ * BeatriceBatch_WrapperBlobBytes: bytes of ONE stream's wrapper blob; 0 where the two calls are refused.
+ * All or nothing, every blob validated before anything is staged.  -1 and no change (no drain, no launch): n < 1 or n > the batch's
+ * streams; a NULL pointer; a stream out of range or named twice; on import a blob with a bad magic word, version, size or check word, a
+ * rate BeatriceBatch_SetStreamRate would refuse, a resampler clock outside [0, hi) of its rate's ratio hi / lo, a FIFO fill outside
+ * [0, 480), a gain that is not finite.  A clock pair in range that no run of calls could have produced may make a later
+ * BeatriceBatch_ProcessBlocksRagged return -2 (its plan's check); it never reads or writes out of bounds.  -2: HIP or allocation failure. */
+size_t BeatriceBatch_WrapperBlobBytes(const BeatriceBatch* b);
+int BeatriceBatch_ExportStreamWrappers(BeatriceBatch* b, int n, const int* streams, void* blobs /* host, n * WrapperBlobBytes(b) */);
+int BeatriceBatch_ImportStreamWrappers(BeatriceBatch* b, int n, const int* streams, const void* blobs /* host, n blobs */);
 /* Throughput form of the any-rate wrapper: the TICK pipeline between resident host-rate blocks (as BeatriceBatch_BindResidentIO48k
  * is for 48 kHz / 0 dB).  d_in / d_out: [n_slots][B][channels][n_samples] planar, at the rate of BeatriceBatch_ConfigureWrapper.
  * Call k = BeatriceBatch_ProcessBlocksDevice(b, NULL, NULL, channels, n_samples) reads slot k mod n_slots; its output block is in
