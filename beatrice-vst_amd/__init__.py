@@ -28,6 +28,7 @@ STEP_WRAP = 12252240  # BEATRICE_HIP_STEP_WRAP (include/beatrice_batch.h): the s
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int)
+_u8p = C.POINTER(C.c_ubyte)
 _vp = C.c_void_p
 
 # name -> (restype, argtypes) for the rc0 generation (include/beatrice_abi.h)
@@ -427,6 +428,10 @@ _BATCH = {
     "BeatriceBatch_MorphSpeaker": (C.c_int, [_vp, C.c_int, _f32p, C.c_int, C.c_uint]),
     "BeatriceBatch_EnableSilentBlockRule": (C.c_int, [_vp, C.c_int]),
     "BeatriceBatch_SetSilentStreams": (C.c_int, [_vp, C.c_char_p]),
+    "BeatriceBatch_ScanSilentBlocksBegin": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, _i32p, _vp]),
+    "BeatriceBatch_ScanSilentBlocksEnd": (C.c_int, [_vp, C.c_int, _u8p]),
+    "BeatriceBatch_ScanSilentBlocks": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, _i32p, _vp, _u8p]),
+    "BeatriceBatch_ScanBoundBlocks48k": (C.c_int, [_vp, C.c_int, _u8p, _u8p, _vp]),
     "BeatriceBatch_BindResidentBlocks": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
     "BeatriceBatch_ResidentBlocksDelay": (C.c_int, [_vp]),
     "BeatriceBatch_ResidentBlocksDelayFor": (C.c_int, [_vp, C.c_int]),
@@ -523,6 +528,7 @@ class Batch:
         t = models.tables if upload_tables else None
         self.B = n_streams
         self.H = hops_per_step
+        self._scans = {}  # ticket -> (n_cells, blocks_per_cell) of the scans begun and not ended (scan_silent_blocks_begin)
         if t is None and max_speakers is None:
             raise ValueError("Batch(upload_tables=False) needs max_speakers: without host tables the table size is unknown")
         ms = max_speakers or (t.n_speakers + 1)
@@ -660,6 +666,45 @@ class Batch:
             raise ValueError("import_stream_wrappers: %d bytes for %d streams of %d bytes each" % (len(blobs), len(idx), self.wrapper_blob_bytes()))
         buf = C.create_string_buffer(bytes(blobs), max(1, len(blobs)))
         self._check(self.a.BeatriceBatch_ImportStreamWrappers(self.h, len(idx), iptr(idx), C.cast(buf, _vp)))
+
+    def scan_silent_blocks_begin(self, d_blocks, n_cells, blocks_per_cell, channels, n_samples, cell_stride=None, cell_samples=None,
+                                 hip_stream=None):
+        """Enqueues the shell's silent-block test over device-resident blocks (BeatriceBatch_ScanSilentBlocksBegin) and returns its
+        ticket for scan_silent_blocks_end.  d_blocks: a device pointer; cell_stride in floats (None: the cells back to back);
+        cell_samples: per-cell lengths (blocks_per_cell = 1).  Up to four tickets may be out; changes nothing of the batch."""
+        if cell_stride is None:
+            cell_stride = blocks_per_cell * channels * n_samples
+        lens = None if cell_samples is None else np.ascontiguousarray(cell_samples, np.int32).reshape(-1)
+        if lens is not None and len(lens) != n_cells:
+            raise ValueError("scan_silent_blocks: %d lengths for %d cells" % (len(lens), n_cells))
+        t = self.a.BeatriceBatch_ScanSilentBlocksBegin(self.h, d_blocks, n_cells, blocks_per_cell, channels, n_samples, cell_stride,
+                                                       None if lens is None else iptr(lens), hip_stream)
+        if t < 0:
+            raise RuntimeError("BeatriceBatch_ScanSilentBlocksBegin failed: %d" % t)
+        self._scans[t] = (n_cells, blocks_per_cell)
+        return t
+
+    def scan_silent_blocks_end(self, ticket):
+        """Waits for that ticket's scan alone and returns its flags, uint8 [n_cells, blocks_per_cell] (1 = silent)."""
+        shape = self._scans.pop(ticket, None)   # (the library gives the ticket up whether the wait succeeds or not)
+        if shape is None:
+            raise RuntimeError("scan_silent_blocks_end: unknown ticket %r" % (ticket,))
+        flags = np.zeros(shape, np.uint8)
+        self._check(self.a.BeatriceBatch_ScanSilentBlocksEnd(self.h, ticket, flags.ctypes.data_as(_u8p)))
+        return flags
+
+    def scan_silent_blocks(self, d_blocks, n_cells, blocks_per_cell, channels, n_samples, cell_stride=None, cell_samples=None, hip_stream=None):
+        """Begin + End: uint8 [n_cells, blocks_per_cell], 1 where every sample of a block's down-mix equals 0.0f."""
+        return self.scan_silent_blocks_end(self.scan_silent_blocks_begin(d_blocks, n_cells, blocks_per_cell, channels, n_samples, cell_stride,
+                                                                         cell_samples, hip_stream))
+
+    def scan_bound_blocks_48k(self, n_calls, hip_stream=None):
+        """With BeatriceBatch_BindResidentIO48k bound: (step_flags uint8 [n_calls, B], block_flags uint8 [n_calls, B, H]) of the slots the
+        next n_calls calls will read; step_flags[k] is what BeatriceBatch_SetSilentStreams takes before the k-th of them."""
+        step = np.zeros((n_calls, self.B), np.uint8)
+        block = np.zeros((n_calls, self.B, self.H), np.uint8)
+        self._check(self.a.BeatriceBatch_ScanBoundBlocks48k(self.h, n_calls, step.ctypes.data_as(_u8p), block.ctypes.data_as(_u8p), hip_stream))
+        return step, block
 
     def close(self):
         if self.h:

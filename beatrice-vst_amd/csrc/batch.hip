@@ -24,6 +24,7 @@
 #include "abi_objects.h"
 #include "batch_modes.h"
 #include "beatrice_batch.h"
+#include "silent_scan_plan.h"
 #include "stream_blob.h"
 #include "tick.hip.h"
 #include "wrapper.hip.h"
@@ -318,6 +319,21 @@ struct BeatriceBatch {
     std::vector<long long> t48_s;                            // [B] 48 kHz samples of the stream fed so far
     std::vector<int> hops_s;                                 // [B] model hops the stream has fired
   } rb;
+  // BeatriceBatch_ScanSilentBlocks* (silent_scan_plan.h, silent_scan.hip): the shell's test on blocks the caller keeps on the device.
+  // Beside the batch, not of it: a stream of its own, a ring of kTickets staging entries -- the kernel's flags on the device, the pinned
+  // copy its one download lands in, the per-cell lengths the kernel reads in place -- each grown by the Begin that needs more, and the
+  // event behind an entry's download.  No step looks at any of it.
+  struct SilentScan {
+    sscan::TicketRing tickets;
+    Stream stream;                       // made by the first call that passes no stream of its own
+    struct Entry {
+      DevBuf<unsigned char> d_flags;     // [cap] one byte per block
+      PinnedBuf<unsigned char> h_flags;  // [cap]
+      PinnedBuf<int> h_len;              // [cap] (cells <= blocks)
+      Event done;
+    } entry[sscan::kTickets];
+    void settle() { for (Entry& e : entry) if (e.done) (void)hipEventSynchronize(e.done); }   // (before the entries are freed)
+  } scan;
 };
 
 namespace {
@@ -965,6 +981,7 @@ void BeatriceBatch_Destroy(BeatriceBatch* b) {
   const DeviceScope dev_(b ? b->device : -1);
   if (!b) return;
   if (b->stream) (void)sync_all(b);
+  b->scan.settle();
   drop_graph(b);
   if (b->own_d_out) { b->wave.d_out = b->own_d_out; b->own_d_out = nullptr; }
   if (b->io_mapped) { b->wave.d_out = b->dev_d_out; b->phone.d_in = b->pitch.d_in = b->d_in; b->io_mapped = false; }  // (the modules free what they allocated)

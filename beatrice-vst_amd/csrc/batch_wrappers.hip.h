@@ -180,6 +180,112 @@ int BeatriceBatch_ConvertBlocks48k(BeatriceBatch* b, const float* in, float* out
   return ok ? 0 : -2;
 }
 
+// ---- the shell's silent-block test on blocks that live on the device (silent_scan_plan.h, silent_scan.hip) ------------
+// What the loop of BeatriceBatch_ConvertBlocks48k above does on host buffers, for a caller whose audio is resident: the flags that
+// BeatriceBatch_SetSilentStreams / ProcessBlocksRaggedDevice's n_samples = 0 take.  A scan is the caller's question about the caller's
+// memory: it runs on a stream of its own (or the caller's), reads no state of the batch but the scan's own ring and -- the bound form --
+// where the resident slots are, and writes none.  Results: the kernel stores one byte per block into the entry's DEVICE buffer and one
+// copy on the scan's stream brings them to the entry's pinned block (not the kernel's own stores over the host link: a byte per
+// wavefront, each its own transaction); the event behind that copy is all an End waits for.
+namespace {
+int scan_begin(BeatriceBatch* b, const float* d_blocks, const sscan::Geometry& g, const int* cell_samples, hipStream_t st) {
+  BeatriceBatch::SilentScan& sc = b->scan;
+  const int e = sc.tickets.free_entry();
+  if (e < 0) return -3;
+  if (!st) {
+    if (!sc.stream && !sc.stream.create("scan stream")) return -2;
+    st = sc.stream;
+  }
+  BeatriceBatch::SilentScan::Entry& en = sc.entry[e];
+  const size_t need = (size_t)g.blocks();
+  if (en.d_flags.size() < need) {   // (a free entry has no reader left: its last End waited for its event)
+    size_t cap = 1024;
+    while (cap < need) cap *= 2;
+    DevBuf<unsigned char> d_flags;
+    PinnedBuf<unsigned char> h_flags;
+    PinnedBuf<int> h_len;
+    if (!d_flags.alloc(cap, "scan flags", false) || !h_flags.alloc(cap, "scan flags host") || !h_len.alloc(cap, "scan lengths")) return -2;
+    en.d_flags = std::move(d_flags); en.h_flags = std::move(h_flags); en.h_len = std::move(h_len);
+  }
+  if (!en.done && !en.done.create("scan event")) return -2;
+  const int* len = nullptr;
+  if (g.ragged) {   // the kernel reads the lengths in place
+    std::memcpy(en.h_len.get(), cell_samples, sizeof(int) * (size_t)g.n_cells);
+    len = en.h_len;
+  }
+  const bool ok = silent_scan(d_blocks, g, sscan::vector_path(d_blocks, g), len, en.d_flags, st) &&
+                  hip_ok(hipMemcpyAsync(en.h_flags.get(), en.d_flags.get(), need, hipMemcpyDeviceToHost, st), "scan flags down") &&
+                  hip_ok(hipEventRecord(en.done, st), "scan event");
+  if (!ok) {   // no ticket is given out, so the entry stays free: whatever of the scan was enqueued is waited for before a later Begin may
+    (void)hipStreamSynchronize(st);   // reuse or regrow the buffers it writes and reads
+    return -2;
+  }
+  return sc.tickets.issue(e, g.blocks());
+}
+int scan_end(BeatriceBatch* b, int ticket, unsigned char* flags) {
+  BeatriceBatch::SilentScan& sc = b->scan;
+  const int e = sc.tickets.entry_of(ticket);
+  if (e < 0) return -1;
+  const bool ok = hip_ok(hipEventSynchronize(sc.entry[e].done), "scan wait");
+  if (ok) std::memcpy(flags, sc.entry[e].h_flags.get(), (size_t)sc.tickets.blocks_of(e));
+  sc.tickets.end(e);
+  return ok ? 0 : -2;
+}
+}  // namespace
+int BeatriceBatch_ScanSilentBlocksBegin(BeatriceBatch* b, const float* d_blocks, int n_cells, int blocks_per_cell, int channels, int n_samples,
+                                        long long cell_stride, const int* cell_samples, void* hip_stream) {
+  BATCH_OPEN(b);
+  sscan::Geometry g;
+  if (!sscan::accept(d_blocks, n_cells, blocks_per_cell, channels, n_samples, cell_stride, cell_samples, true, &g)) return -1;
+  return scan_begin(b, d_blocks, g, cell_samples, static_cast<hipStream_t>(hip_stream));
+}
+int BeatriceBatch_ScanSilentBlocksEnd(BeatriceBatch* b, int ticket, unsigned char* flags) {
+  BATCH_OPEN(b);
+  if (!flags) return -1;
+  return scan_end(b, ticket, flags);
+}
+int BeatriceBatch_ScanSilentBlocks(BeatriceBatch* b, const float* d_blocks, int n_cells, int blocks_per_cell, int channels, int n_samples,
+                                   long long cell_stride, const int* cell_samples, void* hip_stream, unsigned char* flags) {
+  BATCH_OPEN(b);
+  sscan::Geometry g;
+  if (!sscan::accept(d_blocks, n_cells, blocks_per_cell, channels, n_samples, cell_stride, cell_samples, flags != nullptr, &g)) return -1;
+  const int ticket = scan_begin(b, d_blocks, g, cell_samples, static_cast<hipStream_t>(hip_stream));
+  return ticket < 0 ? ticket : scan_end(b, ticket, flags);
+}
+// Mode F: the slots the NEXT n_calls calls of BeatriceBatch_ConvertBlocks48kDevice(b, NULL, NULL, channels) read -- call k reads slot
+// (the host's slot counter + k) mod n_slots, tick_run -- as cells [B][H][channels][480].  The ring of slots may wrap inside the range: two
+// scans then, side by side.
+int BeatriceBatch_ScanBoundBlocks48k(BeatriceBatch* b, int n_calls, unsigned char* step_flags, unsigned char* block_flags, void* hip_stream) {
+  BATCH_ENTER(b, Entry::ConvertBlocks48kDevice_NULL);
+  const BeatriceBatch::Resident48& r = b->r48;
+  const long long per_slot = (long long)b->B * b->H;
+  if (!step_flags || n_calls < 1 || n_calls > r.n_slots || n_calls * per_slot > sscan::kMaxBlocks) return -1;
+  const int first = b->io_host, n1 = std::min(n_calls, r.n_slots - first), n2 = n_calls - n1;
+  const long long cell = (long long)b->H * r.channels * 480;
+  if (b->scan.tickets.free_entries() < (n2 > 0 ? 2 : 1)) return -3;
+  sscan::Geometry g1, g2;
+  const float* p1 = r.d_in48 + (size_t)first * b->B * cell;
+  if (!sscan::accept(p1, (long long)n1 * b->B, b->H, r.channels, 480, cell, nullptr, true, &g1) ||
+      (n2 > 0 && !sscan::accept(r.d_in48, (long long)n2 * b->B, b->H, r.channels, 480, cell, nullptr, true, &g2)))
+    return -1;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const int t1 = scan_begin(b, p1, g1, nullptr, st);
+  if (t1 < 0) return t1;
+  const int t2 = n2 > 0 ? scan_begin(b, r.d_in48, g2, nullptr, st) : 0;
+  std::vector<unsigned char> blocks((size_t)(n_calls * per_slot));
+  int rc = scan_end(b, t1, blocks.data());
+  if (n2 > 0 && t2 >= 0) { const int rc2 = scan_end(b, t2, blocks.data() + (size_t)(n1 * per_slot)); rc = rc ? rc : rc2; }
+  if (t2 < 0) rc = t2;
+  if (rc) return rc;
+  for (long long i = 0; i < n_calls * (long long)b->B; ++i) {   // footnote (6): a stream sits a step out when ALL its blocks of the step are silent
+    unsigned char all = 1;
+    for (int hh = 0; hh < b->H; ++hh) all = all && blocks[(size_t)(i * b->H + hh)];
+    step_flags[i] = all;
+  }
+  if (block_flags) std::memcpy(block_flags, blocks.data(), blocks.size());
+  return 0;
+}
+
 // ---- host-rate blocks with the whole wrapper on the device (wrapper.hip.h) -------------------------------------------
 namespace { constexpr int kInnerStride = wrapn::kMaxSamples + 64; }
 int BeatriceBatch_ConfigureWrapper(BeatriceBatch* b, double sample_rate) {

@@ -332,4 +332,10 @@ struct BlobRound { int n; int streams[16]; int shift[16]; };
 bool stream_gather(const BlobPiece* d_pieces, int n_pieces, const BlobRound& round, float* d_staging, size_t blob_floats, hipStream_t stream);
 bool stream_scatter(const BlobPiece* d_pieces, int n_pieces, const BlobRound& round, const float* d_staging, size_t blob_floats, hipStream_t stream);
 
+// The shell's silent-block test on device-resident blocks (BeatriceBatch_ScanSilentBlocks*; silent_scan.hip, the geometry and the
+// bounds of its reads: silent_scan_plan.h).  d_flags[block] = 1 when every sample of the block's down-mix equals 0.0f; one launch.
+// `vec`: sscan::vector_path's answer for this call.  cell_len: per-cell lengths the device can read (pinned host memory), or nullptr.
+namespace sscan { struct Geometry; }
+bool silent_scan(const float* d_blocks, const sscan::Geometry& g, bool vec, const int* cell_len, unsigned char* d_flags, hipStream_t stream);
+
 }  // namespace bhip

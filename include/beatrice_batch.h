@@ -174,6 +174,9 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *   (9) not rows of this table, because they are settings: BeatriceBatch_SetStreamRate, RestartStreamWrapper, StreamRate, WrapperBlobBytes,
  *       ExportStreamWrappers and ImportStreamWrappers work exactly where the row "ProcessBlocksRagged" says ok -- A and S, one hop per step,
  *       once BeatriceBatch_ConfigureWrapperRates has been called, nothing bound -- and are refused (-1, 0.0 or 0; nothing changes) everywhere else.
+ *   (10) not rows of this table either: BeatriceBatch_ScanSilentBlocksBegin, ScanSilentBlocksEnd and ScanSilentBlocks are questions about the CALLER's
+ *       device memory and work in every mode; BeatriceBatch_ScanBoundBlocks48k works exactly where the row "ConvertBlocks48kDevice(NULL, NULL)" says ok -- F --
+ *       and is refused (-1) everywhere else.  No scan call drains anything, moves a clock, or changes a flag or setting of the batch.
  *
  * Environment variables the library reads: BEATRICE_HIP_DEBUG (print HIP errors to stderr), BEATRICE_HIP_CUMASK ("lo-hi;lo-hi;..": CU masks
  * of the stage-pipelining streams), BEATRICE_HIP_HOP_GRAPH (the 1-stream calls replayed as hipGraphs), BEATRICE_HIP_NO_SPECULATION (no pitch hop beside
@@ -426,6 +429,41 @@ int BeatriceBatch_BindResidentIO48k(BeatriceBatch* b, const float* d_in48, float
  * Returns -1 under host streaming or resident wrapper blocks, and (in order) with resident I/O, stage pipelining or several hops per step. */
 int BeatriceBatch_EnableSilentBlockRule(BeatriceBatch* b, int enable);
 int BeatriceBatch_SetSilentStreams(BeatriceBatch* b, const unsigned char* flags);
+/* The shell's test on blocks that live on the DEVICE: the flags that BeatriceBatch_SetSilentStreams, BeatriceBatch_ConvertBlocks48kDevice and
+ * BeatriceBatch_ProcessBlocksRaggedDevice expect from a caller whose audio never was on the host.  Input: n_cells cells, cell c at float
+ * c * cell_stride of d_blocks; a cell holds blocks_per_cell planar blocks [channels][n_samples] back to back, channels 1 or 2.  With
+ * cell_samples (host, [n_cells]; needs blocks_per_cell = 1) cell c holds ONE block [channels][cell_samples[c]] at its start.  Output: one
+ * byte per block, [n_cells][blocks_per_cell], 1 when every sample of the block's down-mix -- x[i], or (x0[i] + x1[i]) * 0.5f -- equals 0.0f
+ * in float32, exactly the test BeatriceBatch_ConvertBlocks48k makes on host buffers: -0.0 and L = -R are silent, NaN and Inf are not,
+ * subnormals count as the CPU counts them, a block of no samples is silent.  Nothing outside [block, block + channels * length) is read.
+ *   The layouts of the resident modes: D's [n_slots][B][H*160] -- cells n_slots * B, blocks_per_cell H, n_samples 160, mono; G's
+ *   [n_slots][B][channels][n] -- blocks_per_cell 1; P's [n_slots][B][channels * max_samples] with cell_samples = the lengths of the calls
+ *   to come.  In P a block found silent is handed to BeatriceBatch_ProcessBlocksRaggedDevice as n_samples = 0; its output cell is then not
+ *   written and is the caller's to zero.  F's slots: BeatriceBatch_ScanBoundBlocks48k below.
+ * hip_stream: NULL = a non-blocking stream the batch keeps for scans (made by the first such call), so a scan never queues behind the
+ * ticks in flight; or a stream of the caller's, which orders the scan behind whatever produced the blocks.  Either way it is the
+ * CALLER'S PROMISE that the blocks have been written and are visible to that stream when the scan runs, and stay untouched until End.
+ * Begin enqueues the scan and returns a ticket (>= 0); End waits for THAT ticket's scan only and copies its flags out; tickets end in any
+ * order.  Up to four tickets may be outstanding: a fifth Begin returns -3 and changes nothing.  End of an unknown ticket, or of one that
+ * has ended, returns -1.  BeatriceBatch_ScanSilentBlocks is Begin + End.  Begin allocates or grows the staging of its ticket (device and
+ * pinned memory, by the size of the call): it is not a call for an audio thread.
+ * Refused with -1, nothing enqueued: a NULL pointer (d_blocks, flags); n_cells < 1; blocks_per_cell < 1; channels other than 1 or 2;
+ * n_samples < 1 (or > 2^30); cell_stride < blocks_per_cell * channels * n_samples (or > 2^40); cell_samples with blocks_per_cell != 1 or with an entry
+ * outside [0, n_samples]; more than 2^20 blocks in one call.  -2: an unhealthy batch, or a HIP failure.
+ * No scan call drains anything, moves a clock, or changes a flag or setting of the batch (footnote 10 of MODES). */
+int BeatriceBatch_ScanSilentBlocksBegin(BeatriceBatch* b, const float* d_blocks, int n_cells, int blocks_per_cell, int channels, int n_samples,
+                                        long long cell_stride, const int* cell_samples /* host [n_cells] or NULL */, void* hip_stream);
+int BeatriceBatch_ScanSilentBlocksEnd(BeatriceBatch* b, int ticket, unsigned char* flags /* host [n_cells][blocks_per_cell] */);
+int BeatriceBatch_ScanSilentBlocks(BeatriceBatch* b, const float* d_blocks, int n_cells, int blocks_per_cell, int channels, int n_samples,
+                                   long long cell_stride, const int* cell_samples, void* hip_stream, unsigned char* flags);
+/* Mode F (BeatriceBatch_BindResidentIO48k) only, -1 everywhere else: scans the resident input slots that the NEXT n_calls calls of
+ * BeatriceBatch_ConvertBlocks48kDevice(b, NULL, NULL, channels) will read (1 <= n_calls <= n_slots, at most 2^20 blocks), in the binding's
+ * layout [B][H][channels][480], and waits for the answer.  step_flags[k][s] (host, [n_calls][B]) = 1 when ALL H blocks of stream s in the
+ * k-th of those calls are silent: what BeatriceBatch_SetSilentStreams wants before that call at any H (footnote 6).  block_flags (host,
+ * [n_calls][B][H], or NULL) gets every block's own flag.  The rule need not be enabled to scan.  Takes one or two of the four tickets
+ * while it runs (-3 if they are out).  hip_stream and the caller's promise: as above. */
+int BeatriceBatch_ScanBoundBlocks48k(BeatriceBatch* b, int n_calls, unsigned char* step_flags /* [n_calls][B] */,
+                                     unsigned char* block_flags /* [n_calls][B][H] or NULL */, void* hip_stream);
 
 /* The same wrapper at ANY host rate and block size, with the dB-ramped gains (the whole of the reference's
  * ProcessorCore2::Process, src/common/processor_core_2.cc:24-48, per stream on the device): input gain (gain.h:41-71,
