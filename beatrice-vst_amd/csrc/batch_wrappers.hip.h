@@ -796,7 +796,9 @@ static bool rb_bind(BeatriceBatch* b, BeatriceBatch::ResidentBlocks& nr) {
   b->rb = std::move(nr);
   return true;
 }
-// leaves either form of the resident blocks: the pipeline drained, tick mode off, the wrapper restarted at its rate(s)
+// leaves either form of the resident blocks: the pipeline drained, tick mode off, the wrapper restarted at its rate(s).  A restart that
+// fails is not swallowed: -2, the binding is gone, and the wrapper whose state could not be restarted is marked not configured -- its
+// in-order entry points are refused until BeatriceBatch_ConfigureWrapper[Rates] succeeds (what a failed bind leaves, too)
 static int rb_unbind(BeatriceBatch* b) {
   BeatriceBatch::ResidentBlocks& r = b->rb;
   if (!sync_all(b)) return -2;
@@ -809,9 +811,10 @@ static int rb_unbind(BeatriceBatch* b) {
     b->silent.on = false;   // (the flags of the ragged steps were the binding's own)
     std::vector<double> rates(b->B);
     for (int s = 0; s < b->B; ++s) rates[s] = b->rw.classes[b->rw.cls[s]].rate;
-    (void)BeatriceBatch_ConfigureWrapperRates(b, rates.data());
+    if (BeatriceBatch_ConfigureWrapperRates(b, rates.data()) != 0) { b->rw.ready = false; return -2; }
   } else {
-    (void)BeatriceBatch_ConfigureWrapper(b, b->wrap.rate);   // the wrapper restarts, as after a sample-rate change (the gains keep their state)
+    // the wrapper restarts, as after a sample-rate change (the gains keep their state)
+    if (BeatriceBatch_ConfigureWrapper(b, b->wrap.rate) != 0) { b->wrap.ready = false; return -2; }
   }
   return 0;
 }
@@ -926,7 +929,7 @@ int BeatriceBatch_BindResidentBlocks(BeatriceBatch* b, const float* d_in, float*
   const int delay = rb_delay(b, n);
   if (delay < 0 || n_slots < delay + 2) return -1;
   // binding restarts the resampler pair and the FIFO (their in-order form keeps processed samples in the FIFO, this one does not)
-  if (BeatriceBatch_ConfigureWrapper(b, b->wrap.rate) != 0) return -2;
+  if (BeatriceBatch_ConfigureWrapper(b, b->wrap.rate) != 0) { b->wrap.ready = false; return -2; }
   // model hops a call can fire: ceil(inner samples / 480) + 1; a hop's resident output is read until `delay` calls after the
   // call in which the NEXT hop fired.  With H hops per step a slot holds a step: the hops of (delay + 2) calls are that many / H steps.
   const int m_max = (int)std::ceil(n * 48000.0 / b->wrap.rate) + 2, hops_per_call = (m_max + wrapn::kBlock - 1) / wrapn::kBlock + 1;
@@ -1052,7 +1055,7 @@ int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, 
   // binding restarts every stream's resampler pair and FIFO (their in-order form keeps processed samples in the FIFO, this one does not)
   std::vector<double> rates(B);
   for (int s = 0; s < B; ++s) rates[s] = b->rw.classes[b->rw.cls[s]].rate;
-  if (BeatriceBatch_ConfigureWrapperRates(b, rates.data()) != 0) return -2;
+  if (BeatriceBatch_ConfigureWrapperRates(b, rates.data()) != 0) { b->rw.ready = false; return -2; }
   // steps a call can feed = the most hops one stream can fire in it; a hop's resident output is read until `delay` calls after the call
   // in which the stream's NEXT hop fired
   int hops_per_call = 1;
@@ -1081,8 +1084,10 @@ int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, 
 }
 int BeatriceBatch_ResidentBlocksDelay(const BeatriceBatch* b) { return b && b->ok && b->rb.on ? b->rb.delay : -1; }
 int BeatriceBatch_ResidentBlocksDelayFor(const BeatriceBatch* b, int n) { return b && b->ok && b->wrap.ready && n >= 1 ? rb_delay(b, n) : -1; }
-// End of the material: every call made so far gets its output block as if silence had followed (several hops per step: the step still filling
-// is completed with hops of silence -- no caller slot is read or written for them), then the binding starts over as a new one does.
+// End of the material: every call made so far gets its output block as if silence had followed.  Several hops per step: whole made-up blocks
+// of zeros of the binding's length go through the running wrapper (no caller slot is read or written for them; the gain clocks advance
+// through them) until the newest hop a call needs lies in a full step.  Every full step they bring runs, an extra one included; a hop fired
+// beyond the last full step is dropped when the binding then starts over as a new one does (beatrice_batch.h).
 int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b) {
   BATCH_ENTER(b, Entry::FlushResidentBlocks);
   BeatriceBatch::ResidentBlocks& r = b->rb;

@@ -167,7 +167,9 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *   (4) with more resident slots than BeatriceBatch_TickStages() and at most 4096 of them, B <= 4096, H = 1 / 2 / 4.
  *   (6) at H = 2 / 4 a flagged stream sits a WHOLE step (its H hops / its H 48 kHz blocks) out: the caller flags a stream whose blocks of the step are ALL silent.  One
  *       silent block among sounding ones of the same step cannot be skipped there (it is converted as the sounding ones are) -- the shell's per-block rule needs one hop per step.
- *   (5) a bind call on a batch that is already in F / G / P first LEAVES that mode (drains, restarts the wrapper), then binds anew: by the A column, as on any batch.
+ *   (5) a bind call on a batch that is already in F / G / P first LEAVES that mode exactly as that mode's unbind call does, then binds anew: by the A column, as on
+ *       any batch.  G / P: drained, the any-rate wrapper restarted (BeatriceBatch_BindResidentBlocks).  F: drained, and NOTHING restarted -- the 48 kHz wrapper's
+ *       state carries over (BeatriceBatch_BindResidentIO48k).  tests/test_gpu_wrapper_walk.py walks one batch across these transitions against the oracle.
  *   (7) a rule enabled in D / F stays on when the batch leaves tick mode after BeatriceBatch_ConfigureWrapperRates (which keeps the rule's buffers): while it is on,
  *       these calls are refused in C (and a second EnableTickPipeline(1) in D), and EnableSilentBlockRule(1) returns 0.  EnableSilentBlockRule(0) clears it.
  *   (8) H = 1 / 2 / 4: -1 on a batch of eight hops per step.
@@ -408,6 +410,10 @@ int BeatriceBatch_ConvertBlocks48kDevice(BeatriceBatch* b, const float* d_in, fl
  * BeatriceBatch_ConvertBlocks48kDevice(b, NULL, NULL, channels) -- is taken from slot k mod n_slots, and its converted block
  * appears in the same slot of d_out48 BeatriceBatch_TickStages() - 1 calls later or after BeatriceBatch_Synchronize: the
  * samples of the in-order call, later.  NULL, NULL unbinds (and leaves tick mode).
+ * Binding, binding again (another slot count, other buffers: footnote 5 of MODES) and unbinding drain the pipeline and restart NOTHING of a
+ * stream: its 48 kHz wrapper state (the latched model output, the down-sampler's and the up-sampler's histories) and its model state carry
+ * over, so blocks fed in order, then bound, then in order again are, block for block, the samples of ONE in-order run.  The next call
+ * after a bind reads slot 0.
  * On a batch with H = 2 or 4 hops per step (BeatriceBatch_CreateBlock(..., H)) a slot holds H consecutive blocks per stream,
  * [n_slots][B][H][channels][480], and every call converts them all (the samples of H in-order calls). */
 int BeatriceBatch_BindResidentIO48k(BeatriceBatch* b, const float* d_in48, float* d_out48, int channels, int n_slots);
@@ -469,7 +475,11 @@ int BeatriceBatch_ScanBoundBlocks48k(BeatriceBatch* b, int n_calls, unsigned cha
  * ProcessorCore2::Process, src/common/processor_core_2.cc:24-48, per stream on the device): input gain (gain.h:41-71,
  * 2 dB/ms towards the target) -> host rate to 48 kHz (resample.h:130-237: Stern-Brocot ratio, Hann-windowed sinc tables) ->
  * exact-480 FIFO -> every third sample -> model hop -> zero-stuffing -> 48 kHz to host rate -> output gain -> every channel.
- * BeatriceBatch_ConfigureWrapper sets the host rate for the batch (restarting resampler and FIFO, like SetSampleRate);
+ * BeatriceBatch_ConfigureWrapper sets the host rate for the batch and restarts every stream's wrapper as the reference's SetSampleRate
+ * (processor_core_2.cc:421-429) restarts it at a NEW rate: both resampler histories and the 480-sample FIFO become zeros, the two clocks and
+ * the FIFO fill start over; both gains keep their target and their present value and ramp on, at the new rate, from the next block; model
+ * state and settings are untouched.  Unlike SetSampleRate it does so at the PRESENT rate too (the reference: SetSampleRate(another rate),
+ * SetSampleRate(the rate)) -- in mid-life, and after BeatriceBatch_ConfigureWrapperRates, which it replaces;
  * BeatriceBatch_ProcessBlocks[Device] converts one block of n samples per stream, [B][channels][n] planar, channels 1 or 2
  * (stereo is down-mixed (L+R)*0.5 as src/vst/processor.cc:183-192 does; the shell's skip of an all-zero block, :204-214,
  * is NOT applied per stream -- the streams of a batch advance together, a silent stream is converted like any other; the
@@ -540,7 +550,10 @@ int BeatriceBatch_ImportStreamWrappers(BeatriceBatch* b, int n, const int* strea
  * the same slot of d_out BeatriceBatch_ResidentBlocksDelay() (= TickStages() - 1) calls later, or after BeatriceBatch_Synchronize.
  * Gains (BeatriceBatch_SetInputGain / SetOutputGain) and every per-stream setting apply to the call that follows them, as in
  * order.  Same samples as BeatriceBatch_ProcessBlocksDevice in order.  n_slots >= TickStages() + 1.  NULL pointers unbind.
- * Binding and unbinding restart the wrapper (resampler histories, FIFO) as BeatriceBatch_ConfigureWrapper does; gains keep their state.
+ * Binding, binding again without unbinding (another block length, slot count: footnote 5 of MODES) and unbinding each restart the wrapper
+ * (resampler histories, clocks, FIFO) as BeatriceBatch_ConfigureWrapper does; gains keep target and present value, ramps in progress go on;
+ * the streams' model state carries on.  The next call after a bind is call 0 and reads slot 0.  An unbind whose restart fails returns -2:
+ * the binding is gone and the in-order entry points are refused until BeatriceBatch_ConfigureWrapper succeeds.
  * On a batch with H = 2 or 4 hops per step (BeatriceBatch_CreateBlock(..., H); BeatriceBatch_ConfigureWrapper accepts it for this
  * entry point only): the model hops the FIFOs fire are collected H at a time -- hop k of the batch is hop k mod H of step k / H --
  * and a step enters the pipeline when it is full, so every tick launch carries H hops per stream as in plain tick mode; ticks run
@@ -550,17 +563,27 @@ int BeatriceBatch_ImportStreamWrappers(BeatriceBatch* b, int n, const int* strea
  * than two inner samples).  BeatriceBatch_Synchronize drains the ticks and completes the calls whose hops' steps are full; the last
  * calls, which end on a step still filling, stay owed (BeatriceBatch_ResidentBlocksOwed, 0 at one hop per step) until later calls
  * fill it -- an offline caller ends a file with BeatriceBatch_FlushResidentBlocks (or with that many blocks of silence).  Same samples as one
- * hop per step. */
+ * hop per step.  Unbinding or binding again WITHOUT a flush gives the owed calls up: their blocks are never written, and the hops of the step
+ * that was still filling never reach the model (the streams' model state is that of the full steps). */
 int BeatriceBatch_BindResidentBlocks(BeatriceBatch* b, const float* d_in, float* d_out, int channels, int n_samples, int n_slots);
 int BeatriceBatch_ResidentBlocksDelay(const BeatriceBatch* b);
 int BeatriceBatch_ResidentBlocksDelayFor(const BeatriceBatch* b, int n_samples);
 int BeatriceBatch_ResidentBlocksOwed(const BeatriceBatch* b);
 /* End of the material (reference src/common/resample.h:331-364: the FIFO hands a block's samples out one block later -- whatever follows):
- * every call made so far gets its output block, as if blocks of silence had followed -- the library completes the step that is still filling
- * with hops of silence itself (no caller slot is read or written for them), drains the pipeline, runs the output halves still owed --, then
- * the binding STARTS OVER as a new one does: resampler pair and FIFO restarted (the gains keep their state), the next call is call 0 and reads
- * slot 0; the streams' model state carries on.  BeatriceBatch_ResidentBlocksOwed() is 0 afterwards.  With nothing owed (always so at one hop
- * per step and with clocks per stream) it is BeatriceBatch_Synchronize and the binding is left as it is.  -1 without a binding. */
+ * every call made so far gets its output block, as if blocks of silence had followed -- the library makes up calls of its own, each one block
+ * of zeros of the binding's length through the running wrapper (no caller slot is read or written for them, they are not counted as calls),
+ * until the newest hop that a call of the caller's needs lies in a full step; it drains the pipeline and runs the output halves still owed --,
+ * then the binding STARTS OVER as a new one does: resampler pair and FIFO restarted, the next call is call 0 and reads slot 0.
+ * BeatriceBatch_ResidentBlocksOwed() is 0 afterwards.
+ *   Which hops reach the model: a made-up call fires whatever hops its block brings, not just those the open step lacks.  Every FULL step goes
+ *   through the model, a further full step of the last made-up call included -- what a host that went on with that much silence would have
+ *   run.  A hop fired beyond the last full step is DROPPED when the binding starts over: the model never sees it (the reference host would
+ *   have run it; the streams then stand at most H - 1 hops of silence short of it).  The streams' model state carries on from the last full step.
+ *   The gains: their clocks advance through every made-up block as through a caller's block of that length, so a ramp in progress goes on
+ *   (or ends) during the flush; target and present value are kept across the restart, as at BeatriceBatch_ConfigureWrapper.
+ * With nothing owed (always so at one hop per step and with clocks per stream; at several hops per step when the newest hop needed already
+ * lies in a full step) it is BeatriceBatch_Synchronize and the binding is left AS IT IS: nothing restarts, the next call is not call 0 and
+ * reads slot k mod n_slots.  -1 without a binding. */
 int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b);
 /* The throughput form with clocks PER STREAM (reference src/common/resample.h:401-438: every plugin instance owns its resampler
  * pair; here a batch whose streams come from hosts at 44.1, 48, 96 kHz ... with block sizes of their own, around ONE tick pipeline).
@@ -572,7 +595,9 @@ int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b);
  * ragged steps).  The output blocks of call k are in the same slot of d_out BeatriceBatch_ResidentBlocksDelay() (= TickStages() - 1)
  * calls later, or after BeatriceBatch_Synchronize.  Gains and per-stream settings apply to the call that follows them.  Same samples
  * as BeatriceBatch_ProcessBlocksRagged in order = one reference wrapper per stream.  One hop per step, n_slots >= TickStages() + 1.
- * NULL pointers unbind (either bind call unbinds either form); binding and unbinding restart every stream's resampler pair and FIFO. */
+ * NULL pointers unbind (either bind call unbinds either form); binding and unbinding restart every stream's resampler pair and FIFO
+ * (gains keep target and present value).  An unbind whose restart fails returns -2: the binding is gone and the in-order entry points are
+ * refused until BeatriceBatch_ConfigureWrapperRates succeeds. */
 int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, float* d_out, int channels, int max_samples, int n_slots);
 int BeatriceBatch_ProcessBlocksRaggedDevice(BeatriceBatch* b, const int* n_samples);
 

@@ -52,6 +52,15 @@ void* ref_create(double sample_rate, ref_hop_fn fn, void* user) { return new Ref
 void ref_destroy(void* p) { delete static_cast<RefProcessor*>(p); }
 void ref_set_input_gain(void* p, double db) { static_cast<RefProcessor*>(p)->gin.SetTargetGain(db); }
 void ref_set_output_gain(void* p, double db) { static_cast<RefProcessor*>(p)->gout.SetTargetGain(db); }
+// same call sequence as ProcessorCore2::SetSampleRate (reference src/common/processor_core_2.cc:421-429): the reference's own
+// AnyFreqInOut::SetSampleRate (resample.h:425-431) and Gain::Context::SetSampleRate (gain.h:29), where they lie
+void ref_set_sample_rate(void* vp, double sample_rate) {
+  auto* p = static_cast<RefProcessor*>(vp);
+  if (sample_rate == p->chain.GetSampleRate()) return;
+  p->chain.SetSampleRate(sample_rate);
+  p->gin.SetSampleRate(sample_rate);
+  p->gout.SetSampleRate(sample_rate);
+}
 // same call sequence as ProcessorCore2::Process (reference src/common/processor_core_2.cc:44-46)
 int ref_process(void* vp, const float* in, float* out, int n) {
   auto* p = static_cast<RefProcessor*>(vp);

@@ -13,6 +13,8 @@
  *   wo_gain_*          <- Gain::Process / Gain::Context                    src/common/gain.h:19-72
  *   wo_pitch_transform <- ProcessorCore2::Process1 pitch math   src/common/processor_core_2.cc:190-252
  *   wo_process         <- ProcessorCore2::Process               src/common/processor_core_2.cc:44-46
+ *   wo_set_sample_rate <- ProcessorCore2::SetSampleRate         src/common/processor_core_2.cc:421-429
+ *                         (AnyFreqInOut::SetSampleRate resample.h:425-431, Gain::Context::SetSampleRate gain.h:29)
  *
  * PINNED: unlike the neural core, these reference sources compile here; oracle/ref_drivers/
  * ref_wrapper.cc builds them unmodified into oracle/_ref/libref_wrapper.so and
@@ -211,6 +213,24 @@ void wo_destroy(WoProcessor* p) {
   rs_free(&p->rs);
   free(p->io); free(p->work);
   free(p);
+}
+/* A host that changes its rate: nothing at the same rate; otherwise the whole chain is built anew -- tap tables, both clocks, both
+ * filter histories, the 480-sample FIFO (zeros, empty) -- and both gains keep their target and their present value and ramp at the
+ * new rate from the next block on.  The hop callback and whatever the model behind it holds are not touched. */
+void wo_set_sample_rate(WoProcessor* p, double sample_rate) {
+  if (sample_rate == p->sample_rate) return;
+  rs_free(&p->rs);
+  p->sample_rate = sample_rate;
+  rs_init(&p->rs, sample_rate, 48000.0, 0.99 * 16000.0 / clampd(sample_rate, 16000.0, 48000.0),
+          0.99 * 24000.0 / clampd(sample_rate, 24000.0, 48000.0));
+  memset(p->block, 0, sizeof(p->block));
+  p->block_fill = 0;
+  p->gin.sample_rate = p->gout.sample_rate = sample_rate;
+}
+/* what a test needs to know about where a stream stands: samples waiting in the FIFO, and the two gains (dB) */
+int wo_fifo_fill(const WoProcessor* p) { return p->block_fill; }
+void wo_gain_state(const WoProcessor* p, double* in_target, double* in_now, double* out_target, double* out_now) {
+  *in_target = p->gin.target_db; *in_now = p->gin.current_db; *out_target = p->gout.target_db; *out_now = p->gout.current_db;
 }
 void wo_set_input_gain(WoProcessor* p, double db) { p->gin.target_db = db; }
 void wo_set_output_gain(WoProcessor* p, double db) { p->gout.target_db = db; }

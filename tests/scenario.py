@@ -19,7 +19,8 @@ Phase modes are the letters of include/beatrice_batch.h's mode table: A in order
 chunks without waiting; with stage pipelining of depth 2 or 3 underneath in some), D tick mode (with the silent-block rule when the phase
 has sit-outs), E host streaming.  Every phase is entered from A and left to A, along cells the table allows
 (every mode-changing call is asserted to return 0; tests/test_cpu_scenarios.py holds `calls_of()` against csrc/batch_modes.h).  The wrapper
-modes F / G / P and S at 48 kHz are NOT covered here: their reference is the wrapper oracle, another leg.  Morph slots and the codebook
+modes F / G / P and S at 48 kHz are NOT covered here: their reference is the wrapper oracle, another leg: tests/wrapper_walk.py walks one batch across
+the transitions between those modes (tests/test_cpu_wrapper_walk.py, tests/test_gpu_wrapper_walk.py).  Morph slots and the codebook
 lottery are out as well (OracleBatch has no model of them).
 
 Replay one scenario of the list:  python tests/scenario.py --seed N [--B .. --H .. --phases D:40,A:6] [--dump scenario.json] [--gpu]

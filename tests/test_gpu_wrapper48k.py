@@ -138,6 +138,7 @@ def test_48k_wrapper_around_the_tick_pipeline_matches_in_order(bv, oracle, produ
     for k in range(blocks):
         change(ref_batch, k)
         want.append(ref_batch.convert48k(np.ascontiguousarray(x[:, :, 480 * k:480 * (k + 1)]), channels).copy())
+    want_tail = [ref_batch.convert48k(np.ascontiguousarray(x[:, :, 480 * k:480 * (k + 1)]), channels).copy() for k in range(3)]   # (the run simply goes on)
     ref_batch.close()
 
     batch = bv.Batch(m, B)
@@ -176,9 +177,13 @@ def test_48k_wrapper_around_the_tick_pipeline_matches_in_order(bv, oracle, produ
     sample, dev = oracle_leg_48k(bv, oracle, model_dir, B, channels, x, blocks, settings, change, got)
     print("48k wrapper around the tick pipeline vs ORACLE host chain, streams %s, %d blocks: max-abs %g" % (sample, blocks, dev))
     assert dev <= 1e-4
-    # in order again on the same streams (wrapper and model state carried over)
-    y = batch.convert48k(np.ascontiguousarray(x[:, :, :480]), channels)
-    assert np.isfinite(y).all()
+    # in order again on the same streams: wrapper and model state carried over, so the blocks are those of the in-order run that went on
+    # (against the oracle across this transition: tests/test_gpu_wrapper_walk.py, cases F1 / F2)
+    for k in range(3):
+        y = batch.convert48k(np.ascontiguousarray(x[:, :, 480 * k:480 * (k + 1)]), channels)
+        assert np.isfinite(y).all()
+        assert np.array_equal(y, want_tail[k]), "in-order block %d behind the unbind differs" % k
+    assert max(float(np.abs(w).max()) for w in want_tail) > 1e-3
     hip.free(d_in); hip.free(d_out)
     batch.close()
     m.close()

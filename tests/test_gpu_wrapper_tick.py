@@ -145,6 +145,8 @@ def test_any_rate_wrapper_around_the_tick_pipeline(bv, oracle, product, model_di
         k0 += nk
     assert have >= n_real
     got, x = got[:, :, :n_real * block], x[:, :, :n_real * block]
+    # (what the restarted binding COMPUTES -- slot, step counter, FIFO phase, the gains' clocks, which fired hops reached the model -- is held
+    #  against the oracle by tests/test_gpu_wrapper_walk.py, cases U2: every block behind the first flush, bit for bit; here the return codes)
     if use_flush:   # the binding has started over: call 0 reads slot 0 again, the first block out is the FIFO's silence, then sound; a second flush ends it
         buf_in[:min(slots, n_real)] = x[:, :, :min(slots, n_real) * block].reshape(B, channels, -1, block).transpose(2, 0, 1, 3)
         hip.h2d(d_in, buf_in)

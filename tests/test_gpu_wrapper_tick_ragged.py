@@ -40,6 +40,9 @@ def test_mixed_rate_batch_around_the_tick_pipeline_matches_one_proxy_per_stream(
 
     # ---- reference: one proxy on the oracle core per stream, its own rate and block size; absent calls simply do not happen
     want = [np.zeros_like(x[s]) for s in range(B)]
+    tail_call = 2                                           # (a call whose block is silent for no stream: the in-order call behind the unbind feeds it again)
+    assert not any(tail_call in v for v in silent.values())
+    want_tail = []
     for s in range(B):
         p = Proxy(rates[s])
         assert p.call("SetString", K_MODEL, (model_dir + "/model.toml").encode()) == 0
@@ -61,6 +64,16 @@ def test_mixed_rate_batch_around_the_tick_pipeline_matches_one_proxy_per_stream(
             want[s][0, sl] = o0
             if channels == 2:
                 want[s][1, sl] = o1
+        # behind the unbind: the stream's wrapper restarted (SetSampleRate(another rate), SetSampleRate(the rate)), gains and model state
+        # carried over, then one more block
+        assert p.call("SetSampleRate", 8000.0) == 0 and p.call("SetSampleRate", rates[s]) == 0
+        sl = slice(tail_call * n, (tail_call + 1) * n)
+        in0 = np.ascontiguousarray(x[s][0, sl])
+        in1 = np.ascontiguousarray(x[s][1, sl]) if channels == 2 else None
+        o0, o1 = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        assert p.call("ProcessChannels", in0.ctypes.data_as(_f32p), in1.ctypes.data_as(_f32p) if in1 is not None else None,
+                      o0.ctypes.data_as(_f32p), o1.ctypes.data_as(_f32p) if channels == 2 else None, n) == 0
+        want_tail.append(np.stack([o0, o1][:channels]))
         p.close()
 
     # ---- product: one batch, every stream its own clocks, the tick pipeline between resident blocks
@@ -116,11 +129,13 @@ def test_mixed_rate_batch_around_the_tick_pipeline_matches_one_proxy_per_stream(
                 got[s][:, k * n:(k + 1) * n] = out[k % slots, s, :channels * n].reshape(channels, n)
         k0 += nk
     assert a.BeatriceBatch_BindResidentBlocksRagged(h, None, None, 0, 0, 0) == 0
-    # the batch is back in order with its per-stream clocks restarted: one more in-order call goes through
+    # the batch is back in order with its per-stream clocks restarted: one more in-order call, held against the proxies that went on
     ns = (C.c_int * B)(*blocks)
-    xin = np.concatenate([np.ascontiguousarray(x[s][:, :blocks[s]]).reshape(-1) for s in range(B)]).astype(np.float32)
+    xin = np.concatenate([np.ascontiguousarray(x[s][:, tail_call * blocks[s]:(tail_call + 1) * blocks[s]]).reshape(-1) for s in range(B)]).astype(np.float32)
     out = np.zeros_like(xin)
     assert a.BeatriceBatch_ProcessBlocksRagged(h, bv.fptr(xin), bv.fptr(out), channels, ns, 0) == 0
+    offs = np.cumsum([0] + [channels * n for n in blocks])
+    got_tail = [out[offs[s]:offs[s + 1]].reshape(channels, blocks[s]) for s in range(B)]
     batch.close()
     m.close()
     hip.free(d_in)
@@ -133,3 +148,6 @@ def test_mixed_rate_batch_around_the_tick_pipeline_matches_one_proxy_per_stream(
             bad.append("stream %d (%.0f Hz, %d-sample blocks): max-abs %g, first differing call %d" % (
                 s, rates[s], blocks[s], d.max(), int(np.argmax(d.max(axis=0) > 0)) // blocks[s]))
     assert not bad, "; ".join(bad)
+    bad_tail = [s for s in range(B) if not np.array_equal(got_tail[s], want_tail[s])]
+    assert not bad_tail, "the in-order call behind the unbind differs from the proxies in streams %s" % bad_tail
+    assert max(float(np.abs(t).max()) for t in want_tail) > 1e-4     # (more than the restarted FIFOs' zeros: the long blocks reach past 10 ms)

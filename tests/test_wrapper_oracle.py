@@ -101,6 +101,39 @@ def test_vanishing_chain_matches_reference_live(wo, ref, sr, block):
     assert np.abs(want).max() > 1e-3
 
 
+# A host that changes its rate in mid-life (ProcessorCore2::SetSampleRate, processor_core_2.cc:421-429): every leg ends with the FIFO part
+# filled and, from the second leg on, begins with both gain ramps in flight (a change of 40 dB and more set at the leg's start, legs
+# shorter than the 20+ ms such a ramp takes); the fourth leg repeats the third's rate -- the reference's no-op: nothing restarts.
+RATE_WALK_LEGS = [(44100, 441, 1500, -6.0, 3.0), (48000, 480, 700, -46.0, -40.0), (44100, 64, 900, 0.0, 6.0), (44100, 441, 1000, -40.0, -36.0),
+                  (16000, 333, 800, 3.0, 0.0), (96000, 960, 3000, -40.0, 0.0), (44100, 441, 1500, 0.0, 0.0)]
+
+
+def rate_walk_input():
+    return wrapperlib.test_signal(sum(leg[2] for leg in RATE_WALK_LEGS), 44100, seed=4242)
+
+
+def test_set_sample_rate_matches_reference_live(wo, ref):
+    """wo_set_sample_rate against the reference's own AnyFreqInOut::SetSampleRate / Gain::Context::SetSampleRate, live where oracle/_ref is
+    built, and always against its outputs as recorded in golden/wrapper_rate_walk.npz (tools/make_golden.py rate_walk)."""
+    x = rate_walk_input()
+    want = np.load(os.path.join(GOLD, "wrapper_rate_walk.npz"))["walk"]
+    if ref is not None and ref.has_set_rate:
+        a = ref.run_rate_walk(x, RATE_WALK_LEGS)
+        assert np.array_equal(a, want), "recording out of date: max-abs %g" % np.abs(a - want).max()
+    b = wo.run_rate_walk(x, RATE_WALK_LEGS)
+    assert np.array_equal(want, b), "max-abs %g" % np.abs(want - b).max()
+    # what the walk is about is in it: a restart empties the FIFO (the first 10 ms of a leg at a new rate are zeros), the no-op leg has none
+    starts = np.cumsum([0] + [leg[2] for leg in RATE_WALK_LEGS])
+    for i, (sr, _block, _n, _gi, _go) in enumerate(RATE_WALK_LEGS):
+        head = want[starts[i]:starts[i] + int(0.009 * sr)]
+        restarted = i == 0 or RATE_WALK_LEGS[i - 1][0] != sr
+        assert (np.abs(head).max() == 0.0) == restarted, "leg %d" % i
+    assert np.abs(want[starts[-2]:]).max() > 1e-3
+    # a restart at the same rate is SetSampleRate(another rate), SetSampleRate(the rate): not the no-op
+    again = wo.run_rate_walk(x, [leg for i, leg in enumerate(RATE_WALK_LEGS) for leg in ([(8000, 1, 0, leg[3], leg[4])] if i == 3 else []) + [leg]])
+    assert np.array_equal(again[:starts[3]], want[:starts[3]]) and not np.array_equal(again[starts[3]:starts[4]], want[starts[3]:starts[4]])
+
+
 def test_dc_gain_is_half(wo):
     """Zero-stuffing 240 -> 480 has no make-up gain, so DC through an identity-like hop comes out at 0.5
     (SURVEY.md appendix A.3)."""

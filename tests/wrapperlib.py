@@ -34,6 +34,17 @@ class Wrapper:
         self.f_in_gain.argtypes = [C.c_void_p, C.c_double]
         self.f_out_gain = getattr(self.lib, p + "set_output_gain")
         self.f_out_gain.argtypes = [C.c_void_p, C.c_double]
+        # ProcessorCore2::SetSampleRate (processor_core_2.cc:421-429).  A reference library built before the driver had this entry lacks it:
+        # has_set_rate is then False and the tests that want it fall back to their recorded results, as where the library is absent
+        self.has_set_rate = hasattr(self.lib, p + "set_sample_rate")
+        if self.has_set_rate:
+            self.f_set_rate = getattr(self.lib, p + "set_sample_rate")
+            self.f_set_rate.restype, self.f_set_rate.argtypes = None, [C.c_void_p, C.c_double]
+        if prefix == "wo_":   # where a stream stands (the oracle's restatement only): samples waiting in the FIFO; the gains' targets and present values, dB
+            self.f_fifo_fill = self.lib.wo_fifo_fill
+            self.f_fifo_fill.restype, self.f_fifo_fill.argtypes = C.c_int, [C.c_void_p]
+            self.f_gain_state = self.lib.wo_gain_state
+            self.f_gain_state.restype, self.f_gain_state.argtypes = None, [C.c_void_p] + [C.POINTER(C.c_double)] * 4
         self.g_create = getattr(self.lib, p + "gain_create")
         self.g_create.restype, self.g_create.argtypes = C.c_void_p, [C.c_double, C.c_double]
         self.g_set = getattr(self.lib, p + "gain_set_target")
@@ -65,6 +76,35 @@ class Wrapper:
             rc = self.f_process(p, x[pos:pos + n].ctypes.data_as(_f32p), out[pos:pos + n].ctypes.data_as(_f32p), n)
             assert rc == 0
             pos += n
+        self.f_destroy(p)
+        return out
+
+    def gain_state(self, p):
+        """(input target, input now, output target, output now) in dB"""
+        v = [C.c_double(0.0) for _ in range(4)]
+        self.f_gain_state(p, *[C.byref(c) for c in v])
+        return tuple(c.value for c in v)
+
+    def run_rate_walk(self, x, legs, hop=stub_hop):
+        """One processor through a host that changes its rate: legs = [(sample_rate, block, n_samples, input gain dB, output gain dB)];
+        before each leg SetSampleRate(rate) (the first leg creates the processor at its rate), then the two gain targets, then the leg's
+        samples of x in blocks.  A leg at the rate of the one before it is the reference's no-op."""
+        cb = HOP_FN(hop)
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros_like(x)
+        p, pos = None, 0
+        for sr, block, n, gin, gout in legs:
+            if p is None:
+                p = self.f_create(float(sr), cb, None)
+            else:
+                self.f_set_rate(p, float(sr))
+            self.f_in_gain(p, gin)
+            self.f_out_gain(p, gout)
+            end = pos + n
+            while pos < end:
+                m = min(block, end - pos)
+                assert self.f_process(p, x[pos:pos + m].ctypes.data_as(_f32p), out[pos:pos + m].ctypes.data_as(_f32p), m) == 0
+                pos += m
         self.f_destroy(p)
         return out
 

@@ -129,8 +129,25 @@ def reference_cases():
     print("wrapper_vanishing.npz %d bytes, %d arrays" % (os.path.getsize(os.path.join(GOLD, "wrapper_vanishing.npz")), len(v)))
 
 
+def rate_walk():
+    """wrapper_rate_walk.npz: the reference library's result for tests/test_wrapper_oracle.py::test_set_sample_rate_matches_reference_live -- a
+    host that changes its rate in mid-life (SetSampleRate), gains ramping across each change.
+    Run where the reference exists:  make -C oracle && python tools/make_golden.py rate_walk"""
+    ref = wrapperlib.ref_wrapper()
+    if ref is None:
+        raise SystemExit("oracle/_ref/libref_wrapper.so missing: run `make -C oracle` where the reference exists")
+    if not ref.has_set_rate:
+        raise SystemExit("oracle/_ref/libref_wrapper.so is older than oracle/ref_drivers/ref_wrapper.cc: run `make -B -C oracle ref`")
+    import test_wrapper_oracle
+    walk = ref.run_rate_walk(test_wrapper_oracle.rate_walk_input(), test_wrapper_oracle.RATE_WALK_LEGS)
+    np.savez_compressed(os.path.join(GOLD, "wrapper_rate_walk.npz"), walk=walk)
+    print("wrapper_rate_walk.npz %d bytes" % os.path.getsize(os.path.join(GOLD, "wrapper_rate_walk.npz")))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["reference_cases"]:
         reference_cases()
+    elif sys.argv[1:] == ["rate_walk"]:
+        rate_walk()
     else:
         main()

@@ -1,7 +1,8 @@
 #!/bin/bash
 # The CPU-side native code (oracle, C++ host layer: processor core, legacy core, proxy, TOML reader, state blob) under the
 # sanitizers, SURVEY.md section 5:
-#   tools/sanitize_host.sh asan   -> -fsanitize=address,undefined  over the host / oracle / wrapper CPU tests
+#   tools/sanitize_host.sh asan   -> -fsanitize=address,undefined  over the host / oracle / wrapper CPU tests, and over a stand-alone
+#                                    rate walk of the wrapper oracle (tools/sanitize_rate_walk.c)
 #   tools/sanitize_host.sh tsan   -> -fsanitize=thread             over the proxy / state tests + a two-thread stress of the proxy
 # Builds in a scratch copy of the repo (the in-tree .so files are not touched); python runs with the sanitizer runtime preloaded.
 set -e
@@ -28,6 +29,12 @@ else
 fi
 make -s -C oracle CC="gcc $SAN" CXX="g++ $SAN" libbeatrice_oracle.so libhost_on_oracle.so libwrapper_oracle.so liboracle_bench.so
 # (the product library cannot be built here for the sanitizers' sake: tests that need it are the -m gpu ones)
+if [ "$MODE" = asan ]; then
+  # the wrapper oracle's SetSampleRate (wo_set_sample_rate: the chain torn down and rebuilt in mid-life) as a program of its own, nothing preloaded
+  echo "== asan: rate walk of the wrapper oracle (tools/sanitize_rate_walk.c)"
+  gcc $SAN -O1 -std=c11 -Wall -Wextra -o "$WORK/rate_walk" tools/sanitize_rate_walk.c oracle/wrapper_oracle.c -lm
+  ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 timeout 120 "$WORK/rate_walk"
+fi
 echo "== $MODE: pytest $TESTS"
 LD_PRELOAD=$PRELOAD timeout 600 python -m pytest $TESTS -x -q -m "not gpu" -p no:cacheprovider 2>&1 | tail -15
 if [ "$MODE" = tsan ]; then
