@@ -227,7 +227,8 @@ struct BeatriceBatch {
     std::vector<long long> tick_of_ev;         // which tick the event in ev_tick[i] was recorded behind
   } hs;
   // any-rate device wrapper (wrapper.hip.h): the reference host's gains, resampler pair and 480-sample FIFO for all streams
-  wrapn::WrapPlan wrap;
+  wrapn::RateClass wrap;                            // (wrapper_plan.h: everything the host decides about a call)
+  wrapn::Clocks wrap_clk{};
   std::vector<wrapn::GainClock> gain_in, gain_out;  // [B]
   DevBuf<wrapn::StreamState> d_wrap;                // [B]
   DevBuf<float> d_wrap_taps, d_wrap_inner, d_wrap_io;   // taps: down | up; inner [B][kInnerStride]
@@ -267,12 +268,12 @@ struct BeatriceBatch {
   // RagStream): every stream its own host rate, block length and FIFO phase; a stream may sit a call out
   struct RaggedWrap {
     bool ready = false;
-    std::vector<wrapn::WrapPlan> classes;          // one per distinct host rate: ratio and tap tables
+    std::vector<wrapn::RateClass> classes;         // one per distinct host rate: ratio and tap tables
     std::vector<int> cls;                          // [B] class of each stream
-    struct Clock { int phase_down, phase_up, fill; };
-    std::vector<Clock> clk;                        // [B] the stream's two resampler clocks and its FIFO fill
-    std::vector<Clock> clk_undo;                   // what ProcessBlocksRagged restores when a call is refused half-way through its plan
-    std::vector<wrapn::GainClock> gain_undo_in, gain_undo_out;
+    std::vector<wrapn::Clocks> clk;                // [B] the stream's two resampler clocks and its FIFO fill
+    wrapn::CallPlanner next;                       // the state a call being planned would leave: the batch's once every stream's plan stands
+    double rate(int s) const { return classes[cls[s]].rate; }
+    std::vector<double> rates() const { std::vector<double> v(cls.size()); for (size_t s = 0; s < v.size(); ++s) v[s] = rate((int)s); return v; }
     std::vector<int> taps_down_off, taps_up_off;   // per class: float offsets into d_taps
     DevBuf<float> d_taps;
     static constexpr int kStage = 4;
@@ -290,8 +291,9 @@ struct BeatriceBatch {
   // the input half of the chain in front of the ticks, the output half `delay` calls later (wrapper.hip.h wrap_post_kernel)
   struct ResidentBlocks {
     bool on = false;
-    bool dead = false;   // a call of the uniform form failed after the host's clocks had advanced (rb_step): host and device wrapper state no
-                         // longer agree, every further call is refused with -2 until the binding is released
+    bool dead = false;   // a call of the uniform form failed (rb_step).  A plan that is refused moves no clock; what this guards is a failure after
+                         // the commit -- a launch, a tick, the gain ring: host and device wrapper state may no longer agree, every further call
+                         // is refused with -2 until the binding is released
     int channels = 0, n = 0, n_slots = 0, io_slots = 0, delay = 0, ring = 0;
     const float* d_in = nullptr;   // [n_slots][B][channels][n]
     float* d_out = nullptr;        // [n_slots][B][channels][n]

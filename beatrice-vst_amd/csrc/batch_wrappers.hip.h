@@ -292,6 +292,7 @@ int BeatriceBatch_ConfigureWrapper(BeatriceBatch* b, double sample_rate) {
   BATCH_ENTER(b, Entry::ConfigureWrapper);   // (G, P: the binding restarts the wrapper itself when it is made and released; several hops per step: for BeatriceBatch_BindResidentBlocks)
   if (!sync_all(b)) return -2;
   if (!b->wrap.configure(sample_rate)) return -1;  // rate <= 0, or a ratio whose filter history exceeds the state block
+  b->wrap_clk = b->wrap.start();
   const int B = b->B;
   const size_t nt = b->wrap.taps_down.size();
   bool ok = true;
@@ -336,7 +337,9 @@ static bool wrap_chunk(BeatriceBatch* b, const float* d_in, float* d_out, int ch
   using namespace wrapn;
   const int B = b->B;
   hipStream_t st = b->stream;
-  WrapPlan& w = b->wrap;
+  const RateClass& w = b->wrap;
+  ClockPlan p;
+  if (!plan_clocks(w, b->wrap_clk, n, p)) return false;   // (a plan that does not fit: no clock has moved)
   // gains: this call's segment per stream; the device copy is refreshed unless it already holds the same constants
   bool all_constant = true;
   GainSeg* seg = b->wrap_gains.h;
@@ -354,33 +357,18 @@ static bool wrap_chunk(BeatriceBatch* b, const float* d_in, float* d_out, int ch
     b->wrap_gains_constant = all_constant;
   }
   const size_t nt = w.taps_down.size();
-  const Dir din = w.to_inner(n);
-  const int m = din.n_out;
-  if (m < 0 || m > kMaxSamples) return false;
-  hipLaunchKernelGGL(wrap_in_kernel, dim3(B), dim3(256), 0, st, d_in, channels, n, b->d_wrap, b->wrap_gains.d, b->d_wrap_taps + (din.decimate ? 0 : nt), din,
+  hipLaunchKernelGGL(wrap_in_kernel, dim3(B), dim3(256), 0, st, d_in, channels, n, b->d_wrap, b->wrap_gains.d, b->d_wrap_taps + (p.din.decimate ? 0 : nt), p.din,
                      b->d_wrap_inner, kInnerStride);
-  for (int at = 0; at < m;) {  // the exact-480 FIFO; a model hop every time it fills
-    const int take = std::min(kBlock - w.fill, m - at);
-    const int fires = w.fill + take == kBlock ? 1 : 0;
-    hipLaunchKernelGGL(wrap_fifo_kernel, dim3(B), dim3(256), 0, st, b->d_wrap_inner, kInnerStride, b->d_wrap, at, w.fill, take, fires, b->d_in, B_IN_HOP);
-    if (fires) {
-      if (!step_device(b, nullptr, nullptr)) return false;
-      hipLaunchKernelGGL(wrap_refill_kernel, dim3((B * kBlock + 255) / 256), dim3(256), 0, st, b->d_wrap, b->wave.d_out, B);
-      w.fill = 0;
-    } else {
-      w.fill += take;
-    }
-    at += take;
+  for (int c = 0; c < p.cut.n; ++c) {  // the exact-480 FIFO; a model hop every time it fills
+    const int fires = p.cut.fires[c];
+    hipLaunchKernelGGL(wrap_fifo_kernel, dim3(B), dim3(256), 0, st, b->d_wrap_inner, kInnerStride, b->d_wrap, (int)p.cut.at[c], (int)p.cut.fill[c], (int)p.cut.take[c], fires, b->d_in, B_IN_HOP);
+    if (!fires) continue;
+    if (!step_device(b, nullptr, nullptr)) return false;
+    hipLaunchKernelGGL(wrap_refill_kernel, dim3((B * kBlock + 255) / 256), dim3(256), 0, st, b->d_wrap, b->wave.d_out, B);
   }
-  const Dir dout = w.to_outer(m);
-  if (dout.n_out != n) return false;  // the two clocks are coupled so that a block comes back with its own length
   hipLaunchKernelGGL(wrap_out_kernel, dim3(B), dim3(256), 0, st, b->d_wrap_inner, kInnerStride, b->d_wrap, b->wrap_gains.d + B,
-                     b->d_wrap_taps + (dout.decimate ? 0 : nt), dout, d_out, channels);
+                     b->d_wrap_taps + (p.dout.decimate ? 0 : nt), p.dout, d_out, channels);
   return hip_ok(hipGetLastError(), "wrapper launch");
-}
-static int wrap_max_chunk(const BeatriceBatch* b) {  // host samples per launch so that neither side exceeds the kernels' LDS buffers
-  const double r = b->wrap.rate / 48000.0;
-  return std::max(1, (int)std::floor((wrapn::kMaxSamples - 8) * std::min(1.0, r)));
 }
 // in / out: [B][channels][n] planar at the configured host rate; any n >= 1 (long blocks are processed in pieces)
 int BeatriceBatch_ProcessBlocksDevice(BeatriceBatch* b, const float* d_in, float* d_out, int channels, int n) {
@@ -388,15 +376,14 @@ int BeatriceBatch_ProcessBlocksDevice(BeatriceBatch* b, const float* d_in, float
   if (!d_in && !d_out) {   // (G: the next resident block)
     if (channels != b->rb.channels || n != b->rb.n) return -1;
     if (b->rb.dead) return -2;
-    if (!rb_step(b)) { b->rb.dead = true; return -2; }   // (rb_step advances gain clocks, resampler phases and the FIFO before its checks: a failed call leaves the binding unusable, not silently skewed)
+    if (!rb_step(b)) { b->rb.dead = true; return -2; }   // (a call that failed behind its commit -- a launch, a tick, the gain ring -- leaves the binding unusable, not silently skewed)
     return 0;
   }
   if (channels < 1 || channels > 2 || !d_in || !d_out || n < 1) return -1;
-  const int piece = wrap_max_chunk(b);
-  if (n <= piece) return wrap_chunk(b, d_in, d_out, channels, n) ? 0 : -2;
-  return -1;  // the planar layout [B][channels][n] cannot be cut without copies: callers pass blocks of at most `piece` samples
+  if (n > wrapn::longest_block(b->wrap.rate)) return -1;  // the planar layout [B][channels][n] cannot be cut without copies: callers pass blocks of at most that many samples
+  return wrap_chunk(b, d_in, d_out, channels, n) ? 0 : -2;
 }
-int BeatriceBatch_MaxWrapperBlock(const BeatriceBatch* b) { return b && b->ok && b->wrap.ready ? wrap_max_chunk(b) : 0; }
+int BeatriceBatch_MaxWrapperBlock(const BeatriceBatch* b) { return b && b->ok && b->wrap.ready ? wrapn::longest_block(b->wrap.rate) : 0; }
 
 // ---- clocks per stream: a batch whose streams come from different hosts -------------------------------------------------------------
 // rates[B]: the host rate of every stream (streams of equal rate share their tap tables).  Restarts every stream's resampler
@@ -407,13 +394,13 @@ int BeatriceBatch_ConfigureWrapperRates(BeatriceBatch* b, const double* rates) {
   if (!sync_all(b)) return -2;
   BeatriceBatch::RaggedWrap& r = b->rw;
   const int B = b->B;
-  std::vector<wrapn::WrapPlan> classes;
+  std::vector<wrapn::RateClass> classes;
   std::vector<int> cls(B);
   for (int s = 0; s < B; ++s) {
     int c = -1;
     for (size_t i = 0; i < classes.size(); ++i) if (classes[i].rate == rates[s]) { c = (int)i; break; }
     if (c < 0) {
-      wrapn::WrapPlan p;
+      wrapn::RateClass p;
       if (!p.configure(rates[s])) return -1;
       classes.push_back(p);
       c = (int)classes.size() - 1;
@@ -425,7 +412,7 @@ int BeatriceBatch_ConfigureWrapperRates(BeatriceBatch* b, const double* rates) {
   if (!freeze_prepare(b)) return -2;
   std::vector<float> taps;
   std::vector<int> taps_down_off, taps_up_off;
-  for (const wrapn::WrapPlan& p : classes) {
+  for (const wrapn::RateClass& p : classes) {
     taps_down_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_down.begin(), p.taps_down.end());
     taps_up_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_up.begin(), p.taps_up.end());
   }
@@ -442,46 +429,55 @@ int BeatriceBatch_ConfigureWrapperRates(BeatriceBatch* b, const double* rates) {
   if (first) { r.rs = std::move(rs); r.d_frozen = std::move(d_frozen); }
   r.classes = classes;
   r.cls = cls;
-  r.clk.assign(B, BeatriceBatch::RaggedWrap::Clock{0, 0, 0});
-  for (int s = 0; s < B; ++s) r.clk[s] = BeatriceBatch::RaggedWrap::Clock{classes[cls[s]].hi - 1, classes[cls[s]].hi - 1, 0};
+  r.clk.resize(B);
+  for (int s = 0; s < B; ++s) r.clk[s] = classes[cls[s]].start();
   b->wrap.ready = false;          // (the uniform entry points are off until BeatriceBatch_ConfigureWrapper is called again)
   b->wrap_gains_constant = false;
   drop_graph(b);
   r.ready = true;
   return 0;
 }
-// One active stream's share of a call with per-stream clocks: its gain segments, the two resampling directions and the pieces its inner
-// samples are cut into at the 480-sample FIFO, from the stream's own clocks (which advance).  false: the plan does not fit the kernels'
-// buffers -- the caller puts every clock of the call back.
-static bool rag_plan(BeatriceBatch* b, int s, int n, wrapn::RagStream& q, wrapn::GainSeg& seg_in, wrapn::GainSeg& seg_out) {
-  using namespace wrapn;
+// One active stream's share of a call with per-stream clocks, planned on the state the call would leave (rw.next): its gain segments, the
+// two resampling directions and the pieces its inner samples are cut into at the 480-sample FIFO.  false: the plan does not fit the
+// kernels' buffers -- the caller refuses the call, and no clock of any of its streams has moved.
+static bool rag_plan(BeatriceBatch* b, int s, int n, wrapn::RagStream& q, wrapn::GainSeg* seg) {
   BeatriceBatch::RaggedWrap& r = b->rw;
-  WrapPlan& p = r.classes[r.cls[s]];
-  BeatriceBatch::RaggedWrap::Clock& c = r.clk[s];
-  p.phase_down = c.phase_down; p.phase_up = c.phase_up; p.fill = c.fill;   // the class's plan does the clock arithmetic on the stream's state
-  seg_in = b->gain_in[s].advance(n, p.rate);
-  seg_out = b->gain_out[s].advance(n, p.rate);
-  q.din = p.to_inner(n);
-  const int m = q.din.n_out;
-  if (m < 0 || m > kMaxSamples) return false;
-  int fill = p.fill, nc = 0;
-  for (int at = 0; at < m;) {
-    const int take = std::min(kBlock - fill, m - at);
-    if (nc >= kMaxChunks) return false;
-    q.at[nc] = (short)at; q.fill[nc] = (short)fill; q.take[nc] = (short)take;
-    q.fires[nc] = fill + take == kBlock ? 1 : 0;
-    fill = q.fires[nc] ? 0 : fill + take;
-    at += take;
-    ++nc;
-  }
-  q.n_chunks = nc;
-  p.fill = fill;
-  q.dout = p.to_outer(m);
-  if (q.dout.n_out != n) return false;
-  q.taps_in = q.din.decimate ? r.taps_down_off[r.cls[s]] : r.taps_up_off[r.cls[s]];
-  q.taps_out = q.dout.decimate ? r.taps_down_off[r.cls[s]] : r.taps_up_off[r.cls[s]];
-  c.phase_down = p.phase_down; c.phase_up = p.phase_up; c.fill = p.fill;
+  const int c = r.cls[s];
+  wrapn::CallPlan p;
+  if (!r.next.plan(r.classes[c], s, n, p)) return false;
+  q.din = p.din; q.dout = p.dout;
+  p.cut.put(q);
+  q.taps_in = q.din.decimate ? r.taps_down_off[c] : r.taps_up_off[c];
+  q.taps_out = q.dout.decimate ? r.taps_down_off[c] : r.taps_up_off[c];
+  seg[s] = p.gain_in; seg[b->B + s] = p.gain_out;
   return true;
+}
+// the streams that fire a model hop in piece `ci` of such a call: silent.next flags the others for the step that follows
+struct RagFires { bool any, any_out; };
+static RagFires rag_fires(BeatriceBatch* b, const wrapn::RagStream* rs, int ci) {
+  RagFires f{false, false};
+  for (int s = 0; s < b->B; ++s) {
+    const bool fires = rs[s].active && ci < rs[s].n_chunks && rs[s].fires[ci];
+    b->silent.next[s] = fires ? 0 : 1;
+    f.any = f.any || fires; f.any_out = f.any_out || !fires;
+  }
+  return f;
+}
+// Host buffers through the wrapper's pinned staging pair: cnt floats in, what `enqueue(d_in, d_out)` puts on the stream, cnt floats out,
+// everything waited for; zeros where anything failed.
+extern "C++" template <class F>
+static int wrap_round_trip(BeatriceBatch* b, const float* in, float* out, size_t cnt, F enqueue) {
+  const size_t half = (size_t)b->B * 2 * wrapn::kMaxSamples, bytes = sizeof(float) * std::max<size_t>(cnt, 1);
+  float* h_in = b->h_wrap_io; float* h_out = h_in + half; float* d_in = b->d_wrap_io; float* d_out = d_in + half;
+  std::memcpy(h_in, in, sizeof(float) * cnt);
+  bool ok = hip_ok(hipMemcpyAsync(d_in, h_in, bytes, hipMemcpyHostToDevice, b->stream), "wrap in");
+  ok = ok && enqueue(d_in, d_out);
+  ok = ok && hip_ok(hipMemcpyAsync(h_out, d_out, bytes, hipMemcpyDeviceToHost, b->stream), "wrap out");
+  ok = hip_ok(hipStreamSynchronize(b->stream), "wrap sync") && ok;
+  b->inflight = false;
+  if (ok) std::memcpy(out, h_out, sizeof(float) * cnt);
+  else std::memset(out, 0, sizeof(float) * cnt);
+  return ok ? 0 : -2;
 }
 // One call = for every stream s a block of n_samples[s] host samples at ITS rate (0: the stream sits this call out).  in / out:
 // the streams' planar blocks [channels][n_samples[s]] one after the other.  apply_silent_rule != 0: a block whose down-mix is
@@ -497,8 +493,7 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
   hipStream_t st = b->stream;
   size_t total = 0;
   for (int s = 0; s < B; ++s) {
-    if (n_samples[s] < 0) return -1;
-    if (n_samples[s] > 0 && n_samples[s] > std::max(1, (int)std::floor((kMaxSamples - 8) * std::min(1.0, r.classes[r.cls[s]].rate / 48000.0)))) return -1;
+    if (n_samples[s] < 0 || n_samples[s] > longest_block(r.rate(s))) return -1;
     total += (size_t)channels * n_samples[s];
   }
   const int e = (int)(r.calls % r.kStage);
@@ -507,12 +502,9 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
   GainSeg* seg = b->wrap_gains.h;
   int max_chunks = 0;
   size_t off = 0;
-  // (all or nothing: the host-side clocks of the streams planned so far go back to where they were when a later stream's plan does
-  //  not fit -- otherwise host and device state of those streams would part ways)
-  r.clk_undo = r.clk;
-  r.gain_undo_in.assign(b->gain_in.begin(), b->gain_in.end());
-  r.gain_undo_out.assign(b->gain_out.begin(), b->gain_out.end());
-  auto refuse = [&]() { r.clk = r.clk_undo; std::copy(r.gain_undo_in.begin(), r.gain_undo_in.end(), b->gain_in.begin()); std::copy(r.gain_undo_out.begin(), r.gain_undo_out.end(), b->gain_out.begin()); return -2; };
+  // (all or nothing: the streams are planned on the state the call would leave, which becomes the batch's once the last plan stands --
+  //  otherwise host and device state of the streams planned before a refusal would part ways)
+  r.next.begin(r.clk, b->gain_in, b->gain_out);
   for (int s = 0; s < B; ++s) {
     RagStream& q = rs[s];
     q = RagStream{};
@@ -532,60 +524,45 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
     off += (size_t)channels * n;
     q.active = active ? 1 : 0;
     if (!active) { seg[s] = GainSeg{1.0, 1.0, 1.0}; seg[B + s] = GainSeg{1.0, 1.0, 1.0}; continue; }
-    if (!rag_plan(b, s, n, q, seg[s], seg[B + s])) return refuse();
-    const int nc = q.n_chunks;
-    max_chunks = std::max(max_chunks, nc);
+    if (!rag_plan(b, s, n, q, seg)) return -2;
+    max_chunks = std::max(max_chunks, q.n_chunks);
   }
+  r.next.commit(r.clk, b->gain_in, b->gain_out);
   // uploads: the per-stream records of this call, the gain segments, the audio
   RagStream* d_rs = r.rs.dev(e);
-  bool ok = hip_ok(hipMemcpyAsync(d_rs, rs, sizeof(RagStream) * B, hipMemcpyHostToDevice, st), "ragged records up");
-  { const size_t o0 = 0, len = 2 * (size_t)B; GainSeg* dst = nullptr; ok = ok && b->wrap_gains.push_parts(st, 1, &o0, &len, &dst); }
+  bool up = hip_ok(hipMemcpyAsync(d_rs, rs, sizeof(RagStream) * B, hipMemcpyHostToDevice, st), "ragged records up");
+  { const size_t o0 = 0, len = 2 * (size_t)B; GainSeg* dst = nullptr; up = up && b->wrap_gains.push_parts(st, 1, &o0, &len, &dst); }
   b->wrap_gains_constant = false;
-  float* h_in = b->h_wrap_io;
-  float* h_out = b->h_wrap_io + (size_t)B * 2 * kMaxSamples;
-  float* d_in = b->d_wrap_io;
-  float* d_out = b->d_wrap_io + (size_t)B * 2 * kMaxSamples;
-  std::memcpy(h_in, in, sizeof(float) * total);
-  ok = ok && hip_ok(hipMemcpyAsync(d_in, h_in, sizeof(float) * std::max<size_t>(total, 1), hipMemcpyHostToDevice, st), "ragged in");
-  if (!ok) return -2;
-  hipLaunchKernelGGL(wrapr_in_kernel, dim3(B), dim3(256), 0, st, d_in, channels, b->d_wrap, b->wrap_gains.d, r.d_taps, d_rs, b->d_wrap_inner, kInnerStride);
-  BeatriceBatch::SilentRule& sr = b->silent;
-  for (int ci = 0; ci < max_chunks && ok; ++ci) {
-    bool any_fire = false;
-    for (int s = 0; s < B; ++s) {
-      const bool fires = rs[s].active && ci < rs[s].n_chunks && rs[s].fires[ci];
-      sr.next[s] = fires ? 0 : 1;
-      any_fire = any_fire || fires;
+  if (!up) return -2;
+  return wrap_round_trip(b, in, out, total, [&](const float* d_in, float* d_out) {
+    hipLaunchKernelGGL(wrapr_in_kernel, dim3(B), dim3(256), 0, st, d_in, channels, b->d_wrap, b->wrap_gains.d, r.d_taps, d_rs, b->d_wrap_inner, kInnerStride);
+    BeatriceBatch::SilentRule& sr = b->silent;
+    bool ok = true;
+    for (int ci = 0; ci < max_chunks && ok; ++ci) {
+      const RagFires f = rag_fires(b, rs, ci);
+      unsigned char* d_flags = r.d_frozen + (size_t)ci * B;
+      hipLaunchKernelGGL(wrapr_fifo_kernel, dim3(B), dim3(256), 0, st, b->d_wrap_inner, kInnerStride, b->d_wrap, d_rs, ci, b->d_in, d_flags, nullptr, 0, 0);
+      if (!f.any) { std::fill(sr.next.begin(), sr.next.end(), 0); continue; }
+      sr.any_next = f.any_out;
+      if (f.any_out)
+        hipLaunchKernelGGL(freeze_save_kernel, dim3(sr.n_rings, B), dim3(256), 0, st, sr.d_rings, sr.d_keep, B, b->pitch.d_prev_q, sr.d_keep_prev_q);
+      sr.in_block_step = true;
+      ok = step_device(b, nullptr, nullptr);   // (advance_kv / draw_codebooks skip the streams flagged in sr.next)
+      sr.in_block_step = false;
+      std::fill(sr.next.begin(), sr.next.end(), 0);
+      sr.any_next = false;
+      if (!ok) break;
+      if (f.any_out)
+        hipLaunchKernelGGL(freeze_fix_kernel, dim3(sr.n_rings, B), dim3(256), 0, st, sr.d_rings, sr.d_keep, B, d_flags, b->last_hop, b->pitch.d_prev_q, sr.d_keep_prev_q);
+      hipLaunchKernelGGL(wrapr_refill_kernel, dim3((B * kBlock + 255) / 256), dim3(256), 0, st, b->d_wrap, b->wave.d_out, B, d_flags);
     }
-    unsigned char* d_flags = r.d_frozen + (size_t)ci * B;
-    hipLaunchKernelGGL(wrapr_fifo_kernel, dim3(B), dim3(256), 0, st, b->d_wrap_inner, kInnerStride, b->d_wrap, d_rs, ci, b->d_in, d_flags, nullptr, 0, 0);
-    if (!any_fire) { std::fill(sr.next.begin(), sr.next.end(), 0); continue; }
-    bool any_frozen = false;
-    for (int s = 0; s < B; ++s) any_frozen = any_frozen || sr.next[s];
-    sr.any_next = any_frozen;
-    if (any_frozen)
-      hipLaunchKernelGGL(freeze_save_kernel, dim3(sr.n_rings, B), dim3(256), 0, st, sr.d_rings, sr.d_keep, B, b->pitch.d_prev_q, sr.d_keep_prev_q);
-    sr.in_block_step = true;
-    ok = step_device(b, nullptr, nullptr);   // (advance_kv / draw_codebooks skip the streams flagged in sr.next)
-    sr.in_block_step = false;
-    std::fill(sr.next.begin(), sr.next.end(), 0);
-    sr.any_next = false;
-    if (!ok) break;
-    if (any_frozen)
-      hipLaunchKernelGGL(freeze_fix_kernel, dim3(sr.n_rings, B), dim3(256), 0, st, sr.d_rings, sr.d_keep, B, d_flags, b->last_hop, b->pitch.d_prev_q, sr.d_keep_prev_q);
-    hipLaunchKernelGGL(wrapr_refill_kernel, dim3((B * kBlock + 255) / 256), dim3(256), 0, st, b->d_wrap, b->wave.d_out, B, d_flags);
-  }
-  if (ok) {
-    hipLaunchKernelGGL(wrapr_out_kernel, dim3(B), dim3(256), 0, st, b->d_wrap_inner, kInnerStride, b->d_wrap, b->wrap_gains.d + B, r.d_taps, d_rs, d_out, channels);
-    ok = hip_ok(hipGetLastError(), "ragged wrapper launch") && r.rs.mark(e, st);
-  }
-  r.calls += 1;
-  ok = ok && hip_ok(hipMemcpyAsync(h_out, d_out, sizeof(float) * std::max<size_t>(total, 1), hipMemcpyDeviceToHost, st), "ragged out");
-  ok = hip_ok(hipStreamSynchronize(st), "ragged sync") && ok;
-  b->inflight = false;
-  if (ok) std::memcpy(out, h_out, sizeof(float) * total);
-  else std::memset(out, 0, sizeof(float) * total);
-  return ok ? 0 : -2;
+    if (ok) {
+      hipLaunchKernelGGL(wrapr_out_kernel, dim3(B), dim3(256), 0, st, b->d_wrap_inner, kInnerStride, b->d_wrap, b->wrap_gains.d + B, r.d_taps, d_rs, d_out, channels);
+      ok = hip_ok(hipGetLastError(), "ragged wrapper launch") && r.rs.mark(e, st);
+    }
+    r.calls += 1;
+    return ok;
+  });
 }
 
 // ---- one stream's host side on its own: its rate, its restart, its wrapper blob (beatrice_batch.h; the blob: wrapper_blob.h) -------
@@ -600,19 +577,19 @@ bool rag_settings_allowed(const BeatriceBatch* b) { return modes::allowed(Entry:
 // had yet (`fresh`, configured by the caller) follow; classes no stream uses any more are gone.  Unchanged set: nothing is built.
 struct RagTables {
   bool rebuilt = false;
-  std::vector<wrapn::WrapPlan> classes;
+  std::vector<wrapn::RateClass> classes;
   std::vector<int> cls, taps_down_off, taps_up_off;
   DevBuf<float> d_taps;
 };
-bool rag_retable(const BeatriceBatch* b, const std::vector<double>& want, const std::vector<wrapn::WrapPlan>& fresh, RagTables& t) {
+bool rag_retable(const BeatriceBatch* b, const std::vector<double>& want, const std::vector<wrapn::RateClass>& fresh, RagTables& t) {
   const BeatriceBatch::RaggedWrap& r = b->rw;
   const int B = b->B;
   auto used = [&](double rate) { for (int s = 0; s < B; ++s) if (want[s] == rate) return true; return false; };
-  for (const wrapn::WrapPlan& p : r.classes) if (used(p.rate)) t.classes.push_back(p);
+  for (const wrapn::RateClass& p : r.classes) if (used(p.rate)) t.classes.push_back(p);
   t.rebuilt = t.classes.size() != r.classes.size();
-  for (const wrapn::WrapPlan& p : fresh) {
+  for (const wrapn::RateClass& p : fresh) {
     bool have = false;
-    for (const wrapn::WrapPlan& q : t.classes) have = have || q.rate == p.rate;
+    for (const wrapn::RateClass& q : t.classes) have = have || q.rate == p.rate;
     if (!have && used(p.rate)) { t.classes.push_back(p); t.rebuilt = true; }
   }
   t.cls.assign(B, -1);
@@ -621,7 +598,7 @@ bool rag_retable(const BeatriceBatch* b, const std::vector<double>& want, const 
   for (int s = 0; s < B; ++s) if (t.cls[s] < 0) return false;   // (cannot be: every rate wanted is an old class's or a fresh one's)
   if (!t.rebuilt) return true;
   std::vector<float> taps;
-  for (const wrapn::WrapPlan& p : t.classes) {
+  for (const wrapn::RateClass& p : t.classes) {
     t.taps_down_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_down.begin(), p.taps_down.end());
     t.taps_up_off.push_back((int)taps.size()); taps.insert(taps.end(), p.taps_up.begin(), p.taps_up.end());
   }
@@ -637,16 +614,12 @@ void rag_commit(BeatriceBatch* b, RagTables& t) {
   }
   r.cls = std::move(t.cls);
 }
-void rag_rates(const BeatriceBatch* b, std::vector<double>& rates) {
-  rates.resize(b->B);
-  for (int s = 0; s < b->B; ++s) rates[s] = b->rw.classes[b->rw.cls[s]].rate;
-}
 // the class of `rate` among the batch's and those configured so far for this call; a rate none has had is configured (nullptr: refused)
-const wrapn::WrapPlan* rag_class_of(const BeatriceBatch* b, double rate, std::vector<wrapn::WrapPlan>& fresh) {
+const wrapn::RateClass* rag_class_of(const BeatriceBatch* b, double rate, std::vector<wrapn::RateClass>& fresh) {
   if (!std::isfinite(rate)) return nullptr;
-  for (const wrapn::WrapPlan& p : b->rw.classes) if (p.rate == rate) return &p;
-  for (const wrapn::WrapPlan& p : fresh) if (p.rate == rate) return &p;
-  wrapn::WrapPlan p;
+  for (const wrapn::RateClass& p : b->rw.classes) if (p.rate == rate) return &p;
+  for (const wrapn::RateClass& p : fresh) if (p.rate == rate) return &p;
+  wrapn::RateClass p;
   if (!p.configure(rate)) return nullptr;
   fresh.push_back(p);
   return &fresh.back();
@@ -655,10 +628,9 @@ const wrapn::WrapPlan* rag_class_of(const BeatriceBatch* b, double rate, std::ve
 // their state and ramp at the new rate from the next block on
 int rag_restart(BeatriceBatch* b, int s, double rate) {
   BeatriceBatch::RaggedWrap& r = b->rw;
-  std::vector<wrapn::WrapPlan> fresh;
+  std::vector<wrapn::RateClass> fresh;
   if (!rag_class_of(b, rate, fresh)) return -1;
-  std::vector<double> want;
-  rag_rates(b, want);
+  std::vector<double> want = b->rw.rates();
   want[s] = rate;
   RagTables t;
   if (!rag_retable(b, want, fresh, t) || !sync_all(b)) return -2;
@@ -666,8 +638,7 @@ int rag_restart(BeatriceBatch* b, int s, double rate) {
       !hip_ok(hipStreamSynchronize(b->stream), "stream wrapper sync"))
     return -2;
   rag_commit(b, t);
-  const int hi = r.classes[r.cls[s]].hi;
-  r.clk[s] = BeatriceBatch::RaggedWrap::Clock{hi - 1, hi - 1, 0};
+  r.clk[s] = r.classes[r.cls[s]].start();
   b->wrap_gains_constant = false;
   return 0;
 }
@@ -695,17 +666,17 @@ bool wblob_prepare(BeatriceBatch* b, int n) {
 int BeatriceBatch_SetStreamRate(BeatriceBatch* b, int stream, double host_sample_rate) {
   BATCH_OPEN(b);
   if (!rag_settings_allowed(b) || stream < 0 || stream >= b->B) return -1;
-  if (b->rw.classes[b->rw.cls[stream]].rate == host_sample_rate) return 0;   // (the reference's SetSampleRate: an equal rate is no call at all)
+  if (b->rw.rate(stream) == host_sample_rate) return 0;   // (the reference's SetSampleRate: an equal rate is no call at all)
   return rag_restart(b, stream, host_sample_rate);
 }
 int BeatriceBatch_RestartStreamWrapper(BeatriceBatch* b, int stream) {
   BATCH_OPEN(b);
   if (!rag_settings_allowed(b) || stream < 0 || stream >= b->B) return -1;
-  return rag_restart(b, stream, b->rw.classes[b->rw.cls[stream]].rate);
+  return rag_restart(b, stream, b->rw.rate(stream));
 }
 double BeatriceBatch_StreamRate(const BeatriceBatch* b, int stream) {
   if (!b || !b->ok || !rag_settings_allowed(b) || stream < 0 || stream >= b->B) return 0.0;
-  return b->rw.classes[b->rw.cls[stream]].rate;
+  return b->rw.rate(stream);
 }
 size_t BeatriceBatch_WrapperBlobBytes(const BeatriceBatch* b) { return b && b->ok && rag_settings_allowed(b) ? wblob::kBlobBytes : 0; }
 
@@ -726,8 +697,8 @@ int BeatriceBatch_ExportStreamWrappers(BeatriceBatch* b, int n, const int* strea
     for (int j = 0; j < round.n; ++j) {
       const int s = round.streams[j];
       unsigned char* blob = r.h_blob_stage + (size_t)j * wblob::kBlobBytes;
-      const BeatriceBatch::RaggedWrap::Clock& c = r.clk[s];
-      wblob::write_header(r.classes[r.cls[s]].rate, c.phase_down, c.phase_up, c.fill, b->gain_in[s].target_db, b->gain_in[s].now_db,
+      const wrapn::Clocks& c = r.clk[s];
+      wblob::write_header(r.rate(s), c.phase_down, c.phase_up, c.fill, b->gain_in[s].target_db, b->gain_in[s].now_db,
                           b->gain_out[s].target_db, b->gain_out[s].now_db, blob);
       std::memcpy(out + (size_t)(at + j) * wblob::kBlobBytes, blob, wblob::kBlobBytes);
     }
@@ -741,14 +712,13 @@ int BeatriceBatch_ImportStreamWrappers(BeatriceBatch* b, int n, const int* strea
   BeatriceBatch::RaggedWrap& r = b->rw;
   const unsigned char* in = static_cast<const unsigned char*>(blobs);
   std::vector<wblob::Header> taken(n);
-  std::vector<wrapn::WrapPlan> fresh;
-  std::vector<double> want;
-  rag_rates(b, want);
+  std::vector<wrapn::RateClass> fresh;
+  std::vector<double> want = b->rw.rates();
   for (int i = 0; i < n; ++i) {   // every blob is looked at before anything is drained, built, uploaded or written
     const unsigned char* blob = in + (size_t)i * wblob::kBlobBytes;
     double rate = 0.0;
     if (wblob::read_rate(blob, wblob::kBlobBytes, &rate) != wblob::kOk) return -1;
-    const wrapn::WrapPlan* p = rag_class_of(b, rate, fresh);   // (the rate through WrapPlan::configure: its hi bounds the clocks)
+    const wrapn::RateClass* p = rag_class_of(b, rate, fresh);   // (the rate through RateClass::configure: its hi bounds the clocks)
     if (!p || wblob::validate(blob, wblob::kBlobBytes, p->hi, &taken[i]) != wblob::kOk) return -1;
     want[streams[i]] = rate;
   }
@@ -768,7 +738,7 @@ int BeatriceBatch_ImportStreamWrappers(BeatriceBatch* b, int n, const int* strea
   for (int i = 0; i < n; ++i) {
     const int s = streams[i];
     const wblob::Header& h = taken[i];
-    r.clk[s] = BeatriceBatch::RaggedWrap::Clock{h.phase_down, h.phase_up, h.fill};
+    r.clk[s] = wrapn::Clocks{h.phase_down, h.phase_up, h.fill};
     b->gain_in[s].target_db = h.in_target_db; b->gain_in[s].now_db = h.in_now_db;
     b->gain_out[s].target_db = h.out_target_db; b->gain_out[s].now_db = h.out_now_db;
   }
@@ -809,9 +779,7 @@ static int rb_unbind(BeatriceBatch* b) {
   r = {};
   if (ragged) {
     b->silent.on = false;   // (the flags of the ragged steps were the binding's own)
-    std::vector<double> rates(b->B);
-    for (int s = 0; s < b->B; ++s) rates[s] = b->rw.classes[b->rw.cls[s]].rate;
-    if (BeatriceBatch_ConfigureWrapperRates(b, rates.data()) != 0) { b->rw.ready = false; return -2; }
+    if (BeatriceBatch_ConfigureWrapperRates(b, b->rw.rates().data()) != 0) { b->rw.ready = false; return -2; }
   } else {
     // the wrapper restarts, as after a sample-rate change (the gains keep their state)
     if (BeatriceBatch_ConfigureWrapper(b, b->wrap.rate) != 0) { b->wrap.ready = false; return -2; }
@@ -838,42 +806,31 @@ static bool rb_step(BeatriceBatch* b, const bool synthetic) {
   BeatriceBatch::ResidentBlocks& r = b->rb;
   const int B = b->B, n = r.n, H = r.H;
   hipStream_t st = b->stream;
-  WrapPlan& w = b->wrap;
+  const RateClass& w = b->wrap;
   const long long call = r.calls;
   const int ge = (int)(call % r.ring);
   // this call's gain segments: input half now, output half when its job runs.  The kernels read them where they are written (pinned
   // memory): the entry is free again once the output half that read it last has run
   GainSeg* seg = r.gains.claim(ge);
   if (!seg) return false;
+  ClockPlan p;
+  if (!plan_clocks(w, b->wrap_clk, n, p)) return false;   // (a plan that does not fit: no clock has moved)
   for (int s = 0; s < B; ++s) { seg[s] = b->gain_in[s].advance(n, w.rate); seg[B + s] = b->gain_out[s].advance(n, w.rate); }
   const size_t nt = w.taps_down.size();
   WrapCallArgs a{};
-  a.din = w.to_inner(n);
-  const int m = a.din.n_out;
-  if (m < 0 || m > kMaxSamples) return false;
-  const Dir dout = w.to_outer(m);
-  if (dout.n_out != n) return false;
+  a.din = p.din;
   a.src = synthetic ? r.d_zero.get() : r.d_in + (size_t)(call % r.n_slots) * B * r.channels * n;
   a.channels = r.channels; a.n = n; a.st = b->d_wrap; a.gain_in = seg; a.taps_in = b->d_wrap_taps + (a.din.decimate ? 0 : nt);
   a.inner = b->d_wrap_inner; a.stride = kInnerStride; a.in16 = r.d_in16; a.row16 = H * B_IN_HOP; a.B = B; a.H = H;
   // the 480-sample accumulation; a model hop every time it fills (the per-stream FIFO array holds it), into its place: hop
   // hops_fired % H of the step that goes in next -- the steps this call fills take the resident slots from io_host on
+  p.cut.put(a);
   int steps = 0, slot = b->io_host;
-  for (int at = 0; at < m;) {
-    const int take = std::min(kBlock - w.fill, m - at);
-    const int fires = w.fill + take == kBlock ? 1 : 0;
-    if (a.n_chunks >= kMaxChunks) return false;
-    const int c = a.n_chunks++;
-    a.at[c] = (short)at; a.fill[c] = (short)w.fill; a.take[c] = (short)take; a.fires[c] = (unsigned char)fires;
+  for (int c = 0; c < a.n_chunks; ++c) {
     a.in16_off[c] = (long long)((size_t)slot * B * H + (size_t)(r.hops_fired % H)) * B_IN_HOP;
-    if (fires) {
-      ++r.hops_fired;
-      if (r.hops_fired % H == 0) { ++steps; slot = (slot + 1) % r.io_slots; }   // the step is full
-      w.fill = 0;
-    } else {
-      w.fill += take;
-    }
-    at += take;
+    if (!a.fires[c]) continue;
+    ++r.hops_fired;
+    if (r.hops_fired % H == 0) { ++steps; slot = (slot + 1) % r.io_slots; }   // the step is full
   }
   // several hops per step: the output half of the oldest call that is due rides in this launch (its hops left the ticks with the
   // previous call at the latest: `delay` counts this call)
@@ -899,8 +856,8 @@ static bool rb_step(BeatriceBatch* b, const bool synthetic) {
   for (int i = 0; i < steps; ++i) if (!tick_run(b, true)) return false;   // the full steps: into the pipeline
   if (steps == 0 && H == 1 && !tick_run(b, false)) return false;          // one hop per step: the pipeline advances with every call
   r.hops_done = r.hops_fed();
-  if (!synthetic) r.jobs.push_back(BeatriceBatch::ResidentBlocks::Job{call, r.t48, dout});
-  r.t48 += m;
+  if (!synthetic) r.jobs.push_back(BeatriceBatch::ResidentBlocks::Job{call, r.t48, p.dout});
+  r.t48 += p.din.n_out;
   if (!synthetic) r.calls = call + 1;
   bool ok = hip_ok(hipGetLastError(), "wrapper launch");
   // one hop per step: after `delay` calls a call's hops are out, its output half runs behind this call's tick
@@ -925,14 +882,14 @@ int BeatriceBatch_BindResidentBlocks(BeatriceBatch* b, const float* d_in, float*
   BATCH_GATE(b, Entry::BindResidentBlocks_bind);   // (again: the mode the batch is in now that it has left G / P)
   const int stages = b->tk.plan.count();
   const int H = b->H;
-  if (!d_in || !d_out || channels < 1 || channels > 2 || n < 1 || n > wrap_max_chunk(b)) return -1;
+  if (!d_in || !d_out || channels < 1 || channels > 2 || n < 1 || n > wrapn::longest_block(b->wrap.rate)) return -1;
   const int delay = rb_delay(b, n);
   if (delay < 0 || n_slots < delay + 2) return -1;
   // binding restarts the resampler pair and the FIFO (their in-order form keeps processed samples in the FIFO, this one does not)
   if (BeatriceBatch_ConfigureWrapper(b, b->wrap.rate) != 0) { b->wrap.ready = false; return -2; }
   // model hops a call can fire: ceil(inner samples / 480) + 1; a hop's resident output is read until `delay` calls after the
   // call in which the NEXT hop fired.  With H hops per step a slot holds a step: the hops of (delay + 2) calls are that many / H steps.
-  const int m_max = (int)std::ceil(n * 48000.0 / b->wrap.rate) + 2, hops_per_call = (m_max + wrapn::kBlock - 1) / wrapn::kBlock + 1;
+  const int hops_per_call = wrapn::most_hops(n, b->wrap.rate);
   BeatriceBatch::ResidentBlocks nr;
   nr.delay = delay;
   nr.ring = nr.delay + 3;
@@ -956,10 +913,7 @@ static int rbr_step(BeatriceBatch* b, const int* n_samples) {
   BeatriceBatch::RaggedWrap& rw = b->rw;
   const int B = b->B;
   hipStream_t st = b->stream;
-  for (int s = 0; s < B; ++s) {
-    const int lim = std::max(1, (int)std::floor((kMaxSamples - 8) * std::min(1.0, rw.classes[rw.cls[s]].rate / 48000.0)));
-    if (n_samples[s] < 0 || n_samples[s] > std::min(r.max_samples, lim)) return -1;
-  }
+  for (int s = 0; s < B; ++s) if (n_samples[s] < 0 || n_samples[s] > std::min(r.max_samples, longest_block(rw.rate(s)))) return -1;
   const long long call = r.calls;
   const int ge = (int)(call % r.ring);
   // (records and gain segments are read by the kernels where they are written, pinned memory: the ring entry is free again once the
@@ -967,10 +921,8 @@ static int rbr_step(BeatriceBatch* b, const int* n_samples) {
   GainSeg* seg = r.gains.claim(ge);
   if (!seg) return -2;
   RagStream* rs = r.h_rs + (size_t)ge * B;
-  // all or nothing, as BeatriceBatch_ProcessBlocksRagged: a plan that does not fit puts every clock of the call back
-  rw.clk_undo = rw.clk;
-  rw.gain_undo_in.assign(b->gain_in.begin(), b->gain_in.end());
-  rw.gain_undo_out.assign(b->gain_out.begin(), b->gain_out.end());
+  // all or nothing, as BeatriceBatch_ProcessBlocksRagged: the clocks move when every stream's plan stands
+  rw.next.begin(rw.clk, b->gain_in, b->gain_out);
   int max_chunks = 0;
   for (int s = 0; s < B; ++s) {
     RagStream& q = rs[s];
@@ -980,45 +932,31 @@ static int rbr_step(BeatriceBatch* b, const int* n_samples) {
     q.active = n > 0 ? 1 : 0;
     q.hop0 = r.hops_s[s]; q.t0 = r.t48_s[s];
     if (!q.active) { seg[s] = GainSeg{1.0, 1.0, 1.0}; seg[B + s] = GainSeg{1.0, 1.0, 1.0}; continue; }
-    if (!rag_plan(b, s, n, q, seg[s], seg[B + s])) {
-      rw.clk = rw.clk_undo;
-      std::copy(rw.gain_undo_in.begin(), rw.gain_undo_in.end(), b->gain_in.begin());
-      std::copy(rw.gain_undo_out.begin(), rw.gain_undo_out.end(), b->gain_out.begin());
-      return -2;
-    }
+    if (!rag_plan(b, s, n, q, seg)) return -2;
     max_chunks = std::max(max_chunks, q.n_chunks);
   }
+  rw.next.commit(rw.clk, b->gain_in, b->gain_out);
+  bool fire_at[kMaxChunks] = {};   // piece c: does any stream fire in it?
   for (int s = 0; s < B; ++s) {   // (the plan stands: the streams' sample and hop counts move)
     if (!rs[s].active) continue;
     r.t48_s[s] += rs[s].din.n_out;
-    for (int c = 0; c < rs[s].n_chunks; ++c) r.hops_s[s] += rs[s].fires[c];
+    for (int c = 0; c < rs[s].n_chunks; ++c) { r.hops_s[s] += rs[s].fires[c]; fire_at[c] = fire_at[c] || rs[s].fires[c]; }
   }
   // one launch for every stream's input half and FIFO pieces; piece c belongs to the c-th step this call feeds (if any stream fires in
   // it), which takes the next resident slot
   WraprCallArgs a{};
   a.in = r.d_in + (size_t)(call % r.n_slots) * B * r.cell; a.channels = r.channels; a.st = b->d_wrap; a.gain = seg; a.taps_all = rw.d_taps;
   a.rs = rs; a.inner = b->d_wrap_inner; a.stride = kInnerStride; a.in16 = r.d_in16; a.B = B; a.slot_map = r.d_map; a.map_ring = r.map_ring;
-  bool fire_at[kMaxChunks] = {};
-  {
-    int slot = b->io_host;
-    for (int ci = 0; ci < max_chunks; ++ci) {
-      for (int s = 0; s < B && !fire_at[ci]; ++s) fire_at[ci] = rs[s].active && ci < rs[s].n_chunks && rs[s].fires[ci];
-      a.slot[ci] = slot;
-      if (fire_at[ci]) slot = (slot + 1) % r.io_slots;
-    }
+  for (int ci = 0, slot = b->io_host; ci < max_chunks; ++ci) {
+    a.slot[ci] = slot;
+    if (fire_at[ci]) slot = (slot + 1) % r.io_slots;
   }
   hipLaunchKernelGGL(wrapr_call_kernel, dim3(B), dim3(256), 0, st, a);
   BeatriceBatch::SilentRule& sr = b->silent;
   int ticks = 0;
   for (int ci = 0; ci < max_chunks; ++ci) {
     if (!fire_at[ci]) continue;
-    bool any_out = false;
-    for (int s = 0; s < B; ++s) {
-      const bool fires = rs[s].active && ci < rs[s].n_chunks && rs[s].fires[ci];
-      sr.next[s] = fires ? 0 : 1;
-      any_out = any_out || !fires;
-    }
-    sr.any_next = any_out;   // (tick_run: the flagged streams sit this step out, and clears the flags)
+    sr.any_next = rag_fires(b, rs, ci).any_out;   // (tick_run: the flagged streams sit this step out, and clears the flags)
     if (!tick_run(b, true)) return -2;
     std::fill(sr.next.begin(), sr.next.end(), 0);
     sr.any_next = false;
@@ -1053,17 +991,12 @@ int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, 
   if (!d_in || !d_out || channels < 1 || channels > 2 || max_samples < 1 || n_slots < stages + 1) return -1;
   const int B = b->B;
   // binding restarts every stream's resampler pair and FIFO (their in-order form keeps processed samples in the FIFO, this one does not)
-  std::vector<double> rates(B);
-  for (int s = 0; s < B; ++s) rates[s] = b->rw.classes[b->rw.cls[s]].rate;
+  const std::vector<double> rates = b->rw.rates();
   if (BeatriceBatch_ConfigureWrapperRates(b, rates.data()) != 0) { b->rw.ready = false; return -2; }
   // steps a call can feed = the most hops one stream can fire in it; a hop's resident output is read until `delay` calls after the call
   // in which the stream's NEXT hop fired
   int hops_per_call = 1;
-  for (int s = 0; s < B; ++s) {
-    const int lim = std::max(1, (int)std::floor((wrapn::kMaxSamples - 8) * std::min(1.0, rates[s] / 48000.0)));
-    const int m_max = (int)std::ceil(std::min(max_samples, lim) * 48000.0 / rates[s]) + 2;
-    hops_per_call = std::max(hops_per_call, (m_max + wrapn::kBlock - 1) / wrapn::kBlock + 1);
-  }
+  for (int s = 0; s < B; ++s) hops_per_call = std::max(hops_per_call, wrapn::most_hops(std::min(max_samples, wrapn::longest_block(rates[s])), rates[s]));
   BeatriceBatch::ResidentBlocks nr;
   nr.delay = stages - 1;
   nr.ring = nr.delay + 3;
@@ -1115,20 +1048,7 @@ int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b) {
 int BeatriceBatch_ResidentBlocksOwed(const BeatriceBatch* b) { return b && b->ok && b->rb.on ? (int)b->rb.jobs.size() : -1; }
 int BeatriceBatch_ProcessBlocks(BeatriceBatch* b, const float* in, float* out, int channels, int n) {
   BATCH_ENTER(b, Entry::ProcessBlocks);
-  if (channels < 1 || channels > 2 || !in || !out || n < 1 || n > wrap_max_chunk(b)) return -1;
-  const size_t cnt = (size_t)b->B * channels * n;
-  float* h_in = b->h_wrap_io;
-  float* h_out = b->h_wrap_io + (size_t)b->B * 2 * wrapn::kMaxSamples;
-  float* d_in = b->d_wrap_io;
-  float* d_out = b->d_wrap_io + (size_t)b->B * 2 * wrapn::kMaxSamples;
-  std::memcpy(h_in, in, sizeof(float) * cnt);
-  bool ok = hip_ok(hipMemcpyAsync(d_in, h_in, sizeof(float) * cnt, hipMemcpyHostToDevice, b->stream), "wrap in");
-  ok = ok && wrap_chunk(b, d_in, d_out, channels, n);
-  ok = ok && hip_ok(hipMemcpyAsync(h_out, d_out, sizeof(float) * cnt, hipMemcpyDeviceToHost, b->stream), "wrap out");
-  ok = hip_ok(hipStreamSynchronize(b->stream), "wrap sync") && ok;
-  b->inflight = false;
-  if (ok) std::memcpy(out, h_out, sizeof(float) * cnt);
-  else std::memset(out, 0, sizeof(float) * cnt);
-  return ok ? 0 : -2;
+  if (channels < 1 || channels > 2 || !in || !out || n < 1 || n > wrapn::longest_block(b->wrap.rate)) return -1;
+  return wrap_round_trip(b, in, out, (size_t)b->B * channels * n, [&](const float* d_in, float* d_out) { return wrap_chunk(b, d_in, d_out, channels, n); });
 }
 

@@ -11,26 +11,17 @@
 //
 // All streams of a batch share the host rate and the block size and were started together, so everything that is
 // CONTROL -- the two fractional clocks of the resampler pair, how many 48 kHz samples a block yields, the FIFO fill,
-// when a model hop fires -- is the same for every stream and is tracked on the host (WrapPlan); only data lives on the
-// device (per stream: two filter histories and the 480-sample FIFO).  The gains are per-stream settings; the host
+// when a model hop fires -- is the same for every stream and is planned on the host (wrapper_plan.h: a RateClass and its Clocks;
+// the constants, GainSeg and Dir live there too); only data lives on the device (per stream: two filter histories and the
+// 480-sample FIFO).  The gains are per-stream settings; the host
 // keeps each stream's current gain in dB as the reference does (the dB <-> amplitude conversions stay on the host's
 // libm so that they round as the reference's), the device re-creates the per-sample ramp from {start, goal, step}.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <vector>
+#include "wrapper_plan.h"
 
 namespace wrapn {
-
-constexpr int kTapsPerOutput = 32;   // filter length in low-rate samples (reference resample.h:415)
-constexpr int kBlock = 480;          // 10 ms at 48 kHz
-constexpr int kMaxSamples = 4096;    // largest host block per call
-constexpr int kMaxChunks = 12;      // FIFO pieces one call can cut its inner samples into: ceil(4096 / 480) + 2
-constexpr int kMaxHist = kTapsPerOutput * 8 + 1;   // history of the high-rate side: 32 * hi / lo + 1, host rates up to 384 kHz
-
-struct GainSeg { double amp0, goal, step; };   // per stream and call: amplitude before the first sample, goal, per-sample factor
-                                                // (step > 1 ramps up, < 1 down, == 1: constant amp0)
 
 struct StreamState {               // per stream
   float hist_high[kMaxHist];       // newest samples of the high-rate side's filter history (ring replaced by "last H samples")
@@ -38,17 +29,6 @@ struct StreamState {               // per stream
   float hist_high_out[kMaxHist];   // the second direction keeps its own histories
   float hist_low_out[kTapsPerOutput + 1];
   float fifo[kBlock];
-};
-
-// what a resampling direction needs for one call (identical for every stream)
-struct Dir {
-  int decimate;      // 1: high -> low rate (reference Downsample), 0: low -> high (Upsample)
-  int hi, lo;        // rate ratio
-  int phase0;        // the direction's fractional clock before the call
-  int n_in, n_out;
-  int n_taps;        // table length (32 * hi + 1)
-  int hist;          // history length kept between calls
-  float scale;       // Downsample's make-up gain lo / hi
 };
 
 // out[o] of one direction; `x` = [hist | n_in new samples] in LDS.  Tap order and accumulation exactly as the host loops
@@ -479,113 +459,5 @@ static __global__ void wrapr_refill_kernel(StreamState* __restrict__ st, const f
   if (frozen[b]) return;
   st[b].fifo[i] = (i & 1) ? 0.0f : out24[(size_t)b * 240 + (i >> 1)];
 }
-
-// ---- host side: the clocks and the tables -------------------------------------------------------------------------
-// smallest-denominator search on the Stern-Brocot tree, parts < 1000 (reference resample.h:25-46)
-inline void simple_fraction(double ratio, int* numer, int* denom) {
-  int a = 0, b = 1, c = 1, d = 0;
-  for (;;) {
-    const int mn = a + c, md = b + d;
-    const bool big = mn >= 1000 || md >= 1000;
-    if (ratio * md < mn) {
-      if (big) { *numer = a; *denom = b; return; }
-      c = mn; d = md;
-    } else {
-      if (big) { *numer = c; *denom = d; return; }
-      a = mn; b = md;
-    }
-  }
-}
-
-struct WrapPlan {
-  bool ready = false, high_is_outer = true;
-  double rate = 0.0;
-  int hi = 1, lo = 1, phase_down = 0, phase_up = 0, fill = 0;
-  std::vector<float> taps_down, taps_up;
-  int hist_high() const { return kTapsPerOutput * hi / lo + 1; }
-  int hist_low() const { return kTapsPerOutput + 1; }
-  // reference resample.h:209-237 with the cutoffs of :412-417
-  bool configure(double sr) {
-    ready = false;
-    rate = sr;
-    if (!(sr > 0.0)) return false;
-    const double inner = 48000.0, pi = 3.14159265358979323846;
-    const double cutoff_in = 0.99 * 16000.0 / std::fmin(std::fmax(sr, 16000.0), 48000.0), cutoff_out = 0.99 * 24000.0 / std::fmin(std::fmax(sr, 24000.0), 48000.0);
-    high_is_outer = sr >= inner;
-    const double high = high_is_outer ? sr : inner, low = high_is_outer ? inner : sr;
-    const double cut_down = high_is_outer ? cutoff_in : cutoff_out, cut_up = high_is_outer ? cutoff_out : cutoff_in;
-    simple_fraction(high / low, &hi, &lo);
-    if (hi == 0 || lo == 0 || hist_high() > kMaxHist) return false;
-    const int n = kTapsPerOutput * hi + 1, mid = n / 2;
-    taps_down.resize(n);
-    taps_up.resize(n);
-    auto sinc = [pi](double x) { return std::abs(x) < 1e-8 ? 1.0 : std::sin(x * pi) / (x * pi); };
-    for (int i = 0; i < n; ++i) {
-      const double x = static_cast<double>(i - mid) / static_cast<double>(hi);
-      const double hann = 0.5 - 0.5 * std::cos(pi * 2.0 / static_cast<double>(n - 1) * static_cast<double>(i));
-      taps_down[i] = static_cast<float>(cut_down * sinc(x * cut_down) * hann);
-      taps_up[i] = static_cast<float>(cut_up * sinc(x * cut_up) * hann);
-    }
-    phase_down = phase_up = hi - 1;
-    fill = 0;
-    ready = true;
-    return true;
-  }
-  // the direction host -> 48 kHz for a block of n host samples; advances that direction's clock
-  Dir to_inner(int n) {
-    Dir d{};
-    d.hi = hi; d.lo = lo; d.n_in = n; d.n_taps = (int)taps_down.size();
-    if (high_is_outer) {   // Downsample (reference resample.h:130-159)
-      d.decimate = 1; d.phase0 = phase_down; d.hist = hist_high(); d.scale = static_cast<float>(lo) / static_cast<float>(hi);
-      const long long total = phase_down + (long long)n * lo;
-      d.n_out = (int)(total / hi);
-      phase_down = (int)(total % hi);
-    } else {               // Upsample (:168-206)
-      d.decimate = 0; d.phase0 = phase_up; d.hist = hist_low(); d.scale = 1.0f;
-      d.n_out = (int)((((long long)n + 1) * hi - phase_up - 1) / lo);
-      phase_up = (int)((phase_up + (long long)d.n_out * lo) % hi);
-    }
-    return d;
-  }
-  // the direction 48 kHz -> host for m inner samples
-  Dir to_outer(int m) {
-    Dir d{};
-    d.hi = hi; d.lo = lo; d.n_in = m; d.n_taps = (int)taps_up.size();
-    if (high_is_outer) {   // Upsample; the count couples the two clocks (reference resample.h:171-177)
-      d.decimate = 0; d.phase0 = phase_up; d.hist = hist_low(); d.scale = 1.0f;
-      d.n_out = (int)(((long long)m * hi + phase_down - phase_up) / lo);
-      phase_up = (int)((phase_up + (long long)d.n_out * lo) % hi);
-    } else {
-      d.decimate = 1; d.phase0 = phase_down; d.hist = hist_high(); d.scale = static_cast<float>(lo) / static_cast<float>(hi);
-      const long long total = phase_down + (long long)m * lo;
-      d.n_out = (int)(total / hi);
-      phase_down = (int)(total % hi);
-    }
-    return d;
-  }
-};
-
-// the reference's gain context (gain.h:19-72), per stream, on the host: now in dB as a double
-struct GainClock {
-  double target_db = 0.0, now_db = 0.0;
-  static double db_to_amp(double db) { return std::pow(10.0, db * 0.05); }
-  // this call's segment + the state after n samples (the same loop the host layer's GainRamp::Apply runs, without data)
-  GainSeg advance(int n, double rate) {
-    const double goal = db_to_amp(target_db);
-    double amp = db_to_amp(now_db);
-    GainSeg g{amp, goal, 1.0};
-    const double per_sample_db = 2.0 / (rate * 0.001);
-    int i = 0;
-    if (amp < goal) {
-      g.step = db_to_amp(per_sample_db);
-      while (i < n && amp < goal) { amp = std::fmin(amp * g.step, goal); ++i; }
-    } else if (amp > goal) {
-      g.step = db_to_amp(-per_sample_db);
-      while (i < n && amp > goal) { amp = std::fmax(amp * g.step, goal); ++i; }
-    }
-    now_db = 20.0 * std::log10(amp);
-    return g;
-  }
-};
 
 }  // namespace wrapn

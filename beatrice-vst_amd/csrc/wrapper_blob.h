@@ -16,8 +16,8 @@
 //
 // WHAT validate() PROMISES THE KERNELS.  The control fields steer index arithmetic on the device (wrapper.hip.h resample_one, the FIFO
 // pieces), so a blob is only taken if no later call can index out of bounds with it.  hi / lo is the rate's ratio, fixed by the rate alone
-// (WrapPlan::configure, which the batch runs on the blob's rate and which bounds the history by kMaxHist); a call's Dir is made by
-// WrapPlan::to_inner / to_outer from the clocks, and the kernels read x = [hist | n_in] and a tap table of 32 hi + 1 entries:
+// (wrapn::RateClass::configure, wrapper_plan.h, which the batch runs on the blob's rate and which bounds the history by kMaxHist); a call's
+// Dir is made by wrapn::to_inner / to_outer from the class and the clocks, and the kernels read x = [hist | n_in] and a tap table of 32 hi + 1 entries:
 //   decimating (resample_one, d.decimate):  n_out = (phase0 + n_in lo) / hi, so for every o < n_out the input count
 //     k = ceil(((o + 1) hi - phase0) / lo) is <= n_in; with phase0 < hi it is >= 1, and ph = phase0 + k lo - (o + 1) hi lies in [0, lo).
 //     The taps walked are lo - ph, 2 lo - ph, ... below 32 hi: all in [1, 32 hi), and at most ceil((32 hi - 1) / lo) <= 32 hi / lo + 1 =
@@ -29,7 +29,7 @@
 // Both need exactly 0 <= phase < hi of either clock, which validate() checks against the `hi` the caller derived from the blob's own
 // rate.  The FIFO pieces are [fill, fill + take) with take = min(480 - fill, rest): inside the FIFO for 0 <= fill < 480.  A clock pair
 // that is in range but that no run of calls could have produced (the two clocks of a stream are coupled) can make the block count of
-// to_outer differ from the block handed in: the call is then refused with -2 by the plan's existing check (rag_plan), before any launch.
+// to_outer differ from the block handed in: the call is then refused with -2 by the plan's own check (wrapn::plan_clocks), before any launch and with no clock moved.
 // The gain values only feed host arithmetic (GainClock::advance); they must be finite so that a ramp ends.  The state is data.
 #pragma once
 #include <cmath>
@@ -37,14 +37,16 @@
 #include <cstdint>
 #include <cstring>
 
+#include "wrapper_plan.h"
+
 namespace bhip {
 namespace wblob {
 
 constexpr uint32_t kMagic = 0x42575442u;   // "BTWB"
 constexpr uint32_t kVersion = 1;
-constexpr int kFifo = 480;                 // wrapn::kBlock: 10 ms at 48 kHz
-// wrapn::StreamState: two histories of kMaxHist = 32 * 8 + 1 and two of 32 + 1 samples, the FIFO (batch.hip holds the two sizes equal)
-constexpr uint32_t kStateBytes = 4u * (2u * 257u + 2u * 33u + 480u);
+constexpr int kFifo = wrapn::kBlock;       // 10 ms at 48 kHz
+// wrapn::StreamState: two histories of kMaxHist and two of 32 + 1 samples, the FIFO (batch.hip holds the two sizes equal)
+constexpr uint32_t kStateBytes = 4u * (2u * wrapn::kMaxHist + 2u * (wrapn::kTapsPerOutput + 1) + wrapn::kBlock);
 
 struct Header {
   uint32_t magic, version;
@@ -82,7 +84,7 @@ inline void write_header(double rate, int phase_down, int phase_up, int fill, do
 
 enum Refusal { kOk = 0, kTruncated, kMagicBad, kVersionBad, kSizeBad, kCheckBad, kPhaseBad, kFillBad, kGainBad };
 
-// Is `blob` (avail bytes readable) a blob of this build's format?  Its rate comes back: the caller derives hi from it (WrapPlan::configure)
+// Is `blob` (avail bytes readable) a blob of this build's format?  Its rate comes back: the caller derives hi from it (wrapn::RateClass::configure)
 // and then asks validate().
 inline Refusal read_rate(const unsigned char* blob, size_t avail, double* rate) {
   if (avail < sizeof(Header)) return kTruncated;

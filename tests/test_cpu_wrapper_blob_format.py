@@ -109,7 +109,7 @@ int main() {
     CHECK(validate(resealed(blob, [&](Header& h) { h.out_target_db = v; }).data(), kBlobBytes, hi) == kGainBad);
     CHECK(validate(resealed(blob, [&](Header& h) { h.out_now_db = v; }).data(), kBlobBytes, hi) == kGainBad);
   }
-  // the rate is the batch's to judge (WrapPlan::configure): the header only carries it
+  // the rate is the batch's to judge (RateClass::configure): the header only carries it
   CHECK(validate(resealed(blob, [&](Header& h) { h.rate = nan; }).data(), kBlobBytes, hi) == kOk);
   std::printf("ok\n");
   return 0;

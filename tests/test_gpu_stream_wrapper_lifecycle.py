@@ -210,7 +210,7 @@ def move_specs(channels, rule):
     """Source: three streams at 44.1 / 48 / 32 kHz with blocks of 300 / 512 / 300 samples.  Stream 0 -- the one that moves after CALLS calls --
     has, at the move: a speaker switch made one call earlier (a call of 300 samples at 44.1 kHz is 326 or 327 samples at 48 kHz: at most
     one model hop, so at least three of the four key/value blocks are still to come), and an output gain 40 dB away from its target for
-    one call (2 dB/ms: 300 samples at 44.1 kHz move it 13.6 dB).  Its clocks by their own arithmetic (WrapPlan::to_inner / to_outer; 44.1 kHz
+    one call (2 dB/ms: 300 samples at 44.1 kHz move it 13.6 dB).  Its clocks by their own arithmetic (wrapn::to_inner / to_outer, wrapper_plan.h; 44.1 kHz
     is the low side of hi / lo = 160 / 147, so host -> 48 kHz interpolates; both clocks start at hi - 1 = 159): a call of n = 300 samples
     yields m = ((n + 1) x 160 - phase_up - 1) / 147 samples at 48 kHz, 326 or 327, and leaves phase_up = (phase_up + 147 m) mod 160; the way
     back takes (phase_down + 147 m) / 160 = 300 samples and leaves phase_down = (phase_down + 147 m) mod 160.  Over 22 calls that is 7183
@@ -477,7 +477,7 @@ def test_refused_arguments_and_blobs_change_nothing(bv, product, models, good_bl
         for s in (-1, B, 1 << 20):
             assert a.BeatriceBatch_SetStreamRate(h, s, 44100.0) == -1 and a.BeatriceBatch_RestartStreamWrapper(h, s) == -1
             assert a.BeatriceBatch_StreamRate(h, s) == 0.0
-        for rate in (0.0, nan, 1e9, -44100.0, float("inf")):   # what WrapPlan::configure refuses
+        for rate in (0.0, nan, 1e9, -44100.0, float("inf")):   # what RateClass::configure refuses
             assert a.BeatriceBatch_SetStreamRate(h, 1, rate) == -1, rate
         for name, off in h_names.items():   # every header field altered (and the state): the format's own checks
             assert im(1, i32([1]), damaged(off)) == -1, name
