@@ -481,6 +481,9 @@ _BATCH = {
     "BeatriceBatch_WrapperBlobBytes": (C.c_size_t, [_vp]),
     "BeatriceBatch_ExportStreamWrappers": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
     "BeatriceBatch_ImportStreamWrappers": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
+    "BeatriceBatch_SetStreamRateInFlight": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "BeatriceBatch_RestartStreamInFlight": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int]),
+    "BeatriceBatch_BoundStreamRate": (C.c_double, [_vp, C.c_int]),
     "BeatriceBatch_Synchronize": (C.c_int, [_vp]),
     "BeatriceBatch_BindResidentIO": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "BeatriceBatch_SetStream": (C.c_int, [_vp, _vp]),
@@ -644,6 +647,21 @@ class Batch:
     def stream_rate(self, stream):
         """The stream's host rate (0.0 on a batch without clocks per stream)."""
         return float(self.a.BeatriceBatch_StreamRate(self.h, int(stream)))
+
+    def set_stream_rate_in_flight(self, stream, rate):
+        """One stream's SetSampleRate inside a binding with clocks per stream (BeatriceBatch_SetStreamRateInFlight): nothing drains,
+        the owed blocks come out at the old rate, no other stream changes.  A rate the binding has not had allocates: not for an
+        audio thread."""
+        self._check(self.a.BeatriceBatch_SetStreamRateInFlight(self.h, int(stream), float(rate)))
+
+    def restart_stream_in_flight(self, stream, rate=0.0, reset_model=False):
+        """The same restart, also at the present rate (rate = 0.0); reset_model: the stream's next present step is the first step
+        of a new stream -- the slot is turned over to a new caller (BeatriceBatch_RestartStreamInFlight)."""
+        self._check(self.a.BeatriceBatch_RestartStreamInFlight(self.h, int(stream), float(rate), 1 if reset_model else 0))
+
+    def bound_stream_rate(self, stream):
+        """The stream's host rate inside a binding with clocks per stream (0.0 anywhere else)."""
+        return float(self.a.BeatriceBatch_BoundStreamRate(self.h, int(stream)))
 
     def wrapper_blob_bytes(self):
         """Bytes of one stream's wrapper blob (0 where export_stream_wrappers / import_stream_wrappers are refused)."""

@@ -29,6 +29,7 @@
 #include "tick.hip.h"
 #include "wrapper.hip.h"
 #include "wrapper_blob.h"
+#include "wrapper_turnover_plan.h"
 
 using namespace bhip;
 
@@ -276,6 +277,14 @@ struct BeatriceBatch {
     std::vector<double> rates() const { std::vector<double> v(cls.size()); for (size_t s = 0; s < v.size(); ++s) v[s] = rate((int)s); return v; }
     std::vector<int> taps_down_off, taps_up_off;   // per class: float offsets into d_taps
     DevBuf<float> d_taps;
+    // Inside a binding with clocks per stream (BeatriceBatch_SetStreamRateInFlight, wrapper_turnover_plan.h): the classes keep their
+    // index and their place in d_taps while a call that is owed names them -- `arena` slot i is classes[i] (a slot that is not held: a
+    // class that is gone, its index free); new tables go up through pinned staging of the buffer's length; a buffer that was outgrown,
+    // and its staging, wait for the unbind (launches already enqueued hold them)
+    wturn::TapArena arena;
+    PinnedBuf<float> h_taps;
+    std::vector<DevBuf<float>> d_taps_outgrown;
+    std::vector<PinnedBuf<float>> h_taps_outgrown;
     static constexpr int kStage = 4;
     StagedRing<wrapn::RagStream> rs;               // [kStage][B]: a call's per-stream records, pinned staging and device copy
     long long calls = 0;
@@ -320,6 +329,11 @@ struct BeatriceBatch {
     DevBuf<int> d_map;                                       // [B][map_ring]
     std::vector<long long> t48_s;                            // [B] 48 kHz samples of the stream fed so far
     std::vector<int> hops_s;                                 // [B] model hops the stream has fired
+    // a stream that starts over inside the binding (BeatriceBatch_SetStreamRateInFlight / RestartStreamInFlight): t48_s counts from the
+    // restart, hops_s goes on; the record of the stream's next block carries the restart to both wrapper kernels (wrapn::RagStream)
+    std::vector<int> hop_base_s;                             // [B] hops_s at the stream's last restart
+    std::vector<unsigned char> restart_s;                    // [B] the restart has not travelled yet
+    int hops_cap = 0;                                        // hops one stream may fire per call: what io_slots and slot_map were sized for
   } rb;
   // BeatriceBatch_ScanSilentBlocks* (silent_scan_plan.h, silent_scan.hip): the shell's test on blocks the caller keeps on the device.
   // Beside the batch, not of it: a stream of its own, a ring of kTickets staging entries -- the kernel's flags on the device, the pinned

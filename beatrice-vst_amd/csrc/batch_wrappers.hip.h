@@ -426,6 +426,8 @@ int BeatriceBatch_ConfigureWrapperRates(BeatriceBatch* b, const double* rates) {
   ok = ok && hip_ok(hipMemset(b->d_wrap, 0, sizeof(wrapn::StreamState) * B), "ragged state0") && hip_ok(hipDeviceSynchronize(), "ragged sync");
   if (!ok) return -2;
   r.d_taps = std::move(d_taps); r.taps_down_off = taps_down_off; r.taps_up_off = taps_up_off;
+  // (drained: what a binding's rate changes outgrew goes now, wrapper_turnover_plan.h rule 4)
+  r.arena.start(0, 0); r.h_taps.reset(); r.d_taps_outgrown.clear(); r.h_taps_outgrown.clear();
   if (first) { r.rs = std::move(rs); r.d_frozen = std::move(d_frozen); }
   r.classes = classes;
   r.cls = cls;
@@ -930,8 +932,9 @@ static int rbr_step(BeatriceBatch* b, const int* n_samples) {
     const int n = n_samples[s];
     q.io_off = (long long)s * r.cell; q.n = n;
     q.active = n > 0 ? 1 : 0;
-    q.hop0 = r.hops_s[s]; q.t0 = r.t48_s[s];
+    q.hop0 = r.hops_s[s]; q.t0 = r.t48_s[s]; q.hop_base = r.hop_base_s[s];
     if (!q.active) { seg[s] = GainSeg{1.0, 1.0, 1.0}; seg[B + s] = GainSeg{1.0, 1.0, 1.0}; continue; }
+    q.restart = r.restart_s[s];   // (a restart travels with the stream's first block behind it: both halves of this call)
     if (!rag_plan(b, s, n, q, seg)) return -2;
     max_chunks = std::max(max_chunks, q.n_chunks);
   }
@@ -939,6 +942,7 @@ static int rbr_step(BeatriceBatch* b, const int* n_samples) {
   bool fire_at[kMaxChunks] = {};   // piece c: does any stream fire in it?
   for (int s = 0; s < B; ++s) {   // (the plan stands: the streams' sample and hop counts move)
     if (!rs[s].active) continue;
+    r.restart_s[s] = 0;
     r.t48_s[s] += rs[s].din.n_out;
     for (int c = 0; c < rs[s].n_chunks; ++c) { r.hops_s[s] += rs[s].fires[c]; fire_at[c] = fire_at[c] || rs[s].fires[c]; }
   }
@@ -1012,8 +1016,110 @@ int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, 
   r.n_slots = n_slots; r.ragged = true;
   r.t48_s.assign(B, 0);
   r.hops_s.assign(B, 0);
+  r.hop_base_s.assign(B, 0);
+  r.restart_s.assign(B, 0);
+  r.hops_cap = hops_per_call;
+  // the classes as BeatriceBatch_ConfigureWrapperRates has just laid them out: from here on they keep index and place (wrapper_turnover_plan.h)
+  BeatriceBatch::RaggedWrap& rw = b->rw;
+  rw.arena.start(B, r.delay);
+  for (size_t c = 0; c < rw.classes.size(); ++c)
+    rw.arena.add_initial(rw.classes[c].rate, (int)rw.classes[c].taps_down.size(), (int)rw.classes[c].taps_up.size(), (int)std::count(rw.cls.begin(), rw.cls.end(), (int)c));
   r.on = true;
   return 0;
+}
+// ---- a stream's rate, its restart and its slot's turn-over INSIDE that binding (beatrice_batch.h; the tap tables: wrapper_turnover_plan.h) -------
+// Nothing drains, nothing is waited for, no tick runs: the host's clocks start over here, the device learns of it from the record of the
+// stream's next block (rbr_step, wrapn::RagStream), and the calls that are owed finish on the old rate, taps and output history.  Everything
+// that can be refused or can fail -- the rate, the room for its hops, the table's place, buffer and upload, the reset table -- comes before
+// the first thing that is committed.
+namespace {
+bool rbr_settings_allowed(const BeatriceBatch* b) { return modes::allowed(Entry::ProcessBlocksRaggedDevice, flags_of(b)); }
+// a rate no held class has: its class gets a place in the tap buffer and goes up; its index (-2: no room, or HIP failed -- nothing is changed)
+int rbr_place(BeatriceBatch* b, wrapn::RateClass& fresh) {
+  BeatriceBatch::RaggedWrap& rw = b->rw;
+  wturn::TapArena& ar = rw.arena;
+  const double rate = fresh.rate;
+  const int n_down = (int)fresh.taps_down.size(), n_up = (int)fresh.taps_up.size(), floats = n_down + n_up;
+  ar.reap(b->rb.calls);
+  const wturn::Place p = ar.plan(floats);
+  if (p.index < 0) return -2;
+  auto put = [](float* h, int off, const wrapn::RateClass& k) {
+    std::memcpy(h + off, k.taps_down.data(), sizeof(float) * k.taps_down.size());
+    std::memcpy(h + off + k.taps_down.size(), k.taps_up.data(), sizeof(float) * k.taps_up.size());
+  };
+  if (p.grows || !rw.h_taps) {
+    // a longer buffer (or the first staging): every held class at its old offset, the new one behind them, one copy; the launches to
+    // come get this buffer, the ones enqueued keep theirs
+    DevBuf<float> d_taps;
+    PinnedBuf<float> h_taps;
+    if ((p.grows && !d_taps.alloc((size_t)p.capacity, "ragged taps", false)) || !h_taps.alloc((size_t)p.capacity, "ragged taps staging")) return -2;
+    int end = p.off + floats;
+    for (size_t i = 0; i < ar.slots.size(); ++i) {
+      if (!ar.slots[i].held) continue;
+      put(h_taps, ar.slots[i].off, rw.classes[i]);
+      end = std::max(end, ar.slots[i].off + ar.slots[i].floats);
+    }
+    put(h_taps, p.off, fresh);
+    const bool ok = p.grows ? hip_ok(hipMemcpyAsync(d_taps, h_taps, sizeof(float) * (size_t)end, hipMemcpyHostToDevice, b->stream), "ragged taps up")
+                            : hip_ok(hipMemcpyAsync(rw.d_taps + p.off, h_taps + p.off, sizeof(float) * (size_t)floats, hipMemcpyHostToDevice, b->stream), "ragged class up");
+    if (!ok) { (void)hipStreamSynchronize(b->stream); return -2; }   // (the staging is about to go: nothing may still read it)
+    if (p.grows) { rw.d_taps_outgrown.push_back(std::move(rw.d_taps)); rw.d_taps = std::move(d_taps); }
+    if (rw.h_taps) rw.h_taps_outgrown.push_back(std::move(rw.h_taps));
+    rw.h_taps = std::move(h_taps);
+  } else {
+    put(rw.h_taps, p.off, fresh);   // (a free place: no copy that matters is pending on these floats, rule 3)
+    if (!hip_ok(hipMemcpyAsync(rw.d_taps + p.off, rw.h_taps + p.off, sizeof(float) * (size_t)floats, hipMemcpyHostToDevice, b->stream), "ragged class up")) return -2;
+  }
+  ar.commit(p, rate, n_down, n_up);
+  const int c = p.index;
+  if ((int)rw.classes.size() <= c) { rw.classes.resize(c + 1); rw.taps_down_off.resize(c + 1); rw.taps_up_off.resize(c + 1); }
+  rw.classes[c] = std::move(fresh);
+  rw.taps_down_off[c] = ar.slots[c].off_down(); rw.taps_up_off[c] = ar.slots[c].off_up();
+  return c;
+}
+int rbr_restart(BeatriceBatch* b, int s, double rate, bool reset_model) {
+  BeatriceBatch::ResidentBlocks& r = b->rb;
+  BeatriceBatch::RaggedWrap& rw = b->rw;
+  if (!std::isfinite(rate)) return -1;
+  const int old = rw.cls[s];
+  int c = rate == rw.rate(s) ? old : rw.arena.find(rate);
+  wrapn::RateClass fresh;
+  if (c < 0 && !fresh.configure(rate)) return -1;   // (what BeatriceBatch_SetStreamRate refuses)
+  if (wrapn::most_hops(std::min(r.max_samples, wrapn::longest_block(rate)), rate) > r.hops_cap) return -1;   // (the slot ring and slot map: sized at bind time)
+  if (reset_model && !tick_reset_prepare(b)) return -2;
+  if (c < 0) c = rbr_place(b, fresh);
+  if (c < 0) return c;
+  if (c != old) {   // (nothing below fails)
+    rw.arena.join(c, r.calls);
+    rw.arena.leave(old, r.calls);
+    rw.cls[s] = c;
+  }
+  rw.clk[s] = rw.classes[c].start();
+  r.t48_s[s] = 0;
+  r.hop_base_s[s] = r.hops_s[s];
+  r.restart_s[s] = 1;
+  if (!reset_model) return 0;
+  // the slot goes to a new caller: what BeatriceBatch_ResetStreamInFlight does in plain tick mode -- the stream's next present step is
+  // the first of a new stream (tick_run carries the reset to it, also past steps it sits out), all four key/value blocks installed there
+  b->tk.reset_pending[s] = 1;
+  b->tk.any_reset_pending = true;
+  return BeatriceBatch_FlushSpeaker(b, s);
+}
+}  // namespace
+int BeatriceBatch_SetStreamRateInFlight(BeatriceBatch* b, int stream, double host_sample_rate) {
+  BATCH_OPEN(b);
+  if (!rbr_settings_allowed(b) || stream < 0 || stream >= b->B) return -1;
+  if (b->rw.rate(stream) == host_sample_rate) return 0;   // (the reference's SetSampleRate: an equal rate is no call at all)
+  return rbr_restart(b, stream, host_sample_rate, false);
+}
+int BeatriceBatch_RestartStreamInFlight(BeatriceBatch* b, int stream, double host_sample_rate, int reset_model) {
+  BATCH_OPEN(b);
+  if (!rbr_settings_allowed(b) || stream < 0 || stream >= b->B) return -1;
+  return rbr_restart(b, stream, host_sample_rate == 0.0 ? b->rw.rate(stream) : host_sample_rate, reset_model != 0);
+}
+double BeatriceBatch_BoundStreamRate(const BeatriceBatch* b, int stream) {
+  if (!b || !b->ok || !rbr_settings_allowed(b) || stream < 0 || stream >= b->B) return 0.0;
+  return b->rw.rate(stream);
 }
 int BeatriceBatch_ResidentBlocksDelay(const BeatriceBatch* b) { return b && b->ok && b->rb.on ? b->rb.delay : -1; }
 int BeatriceBatch_ResidentBlocksDelayFor(const BeatriceBatch* b, int n) { return b && b->ok && b->wrap.ready && n >= 1 ? rb_delay(b, n) : -1; }

@@ -264,6 +264,15 @@ struct RagStream {
   // around the tick pipeline (BeatriceBatch_BindResidentBlocksRagged): the stream's own 48 kHz sample count and model-hop count
   // at the start of the call
   int hop0;
+  // ... and a stream that starts over inside the binding (BeatriceBatch_SetStreamRateInFlight / RestartStreamInFlight): the restart
+  // travels in the record of the stream's first block behind it, because the two halves of that call run `delay` calls apart and the
+  // output halves of the calls in between still need the old output history (a memset on the stream would sit in front of them).
+  // restart != 0: both halves take their filter history as zeros.  t0 counts the stream's 48 kHz samples from the restart, its hop
+  // numbers do NOT start again (slot_map still holds the old hops' entries for the output halves that are owed): hop_base is the
+  // stream's hop count at the restart, so sample t comes from hop hop_base + t / 480 - 1.  The 480-sample FIFO needs nothing: around the
+  // ticks nobody reads what it hands back, and a hop takes all 480 places, each written since the fill started over at 0.
+  int hop_base;
+  int restart;
   long long t0;
 };
 
@@ -286,7 +295,8 @@ __device__ __forceinline__ void wrapr_in_body(float* __restrict__ x, double* __r
     }
   }
   const float* tl_ = stage_taps(d, taps, tid);
-  for (int i = tid; i < d.hist; i += 256) x[i] = hist[i];
+  if (r.restart) { for (int i = tid; i < d.hist; i += 256) x[i] = 0.0f; }   // (uniform over the workgroup: the record is)
+  else for (int i = tid; i < d.hist; i += 256) x[i] = hist[i];
   __syncthreads();
   for (int i = tid; i < n; i += 256) {
     float m = src[i];
@@ -407,7 +417,10 @@ static __global__ __launch_bounds__(256) void wrapr_call_kernel(const WraprCallA
 }
 // The output half of a call with per-stream clocks around the tick pipeline: as wrap_post_kernel, with the stream's own sample
 // count t0 and its own hops -- 48 kHz sample t of stream b is sample t % 480 of the zero-stuffed output of ITS hop t / 480 - 1, which
-// rode in the step of resident slot slot_map[b][hop mod map_ring].
+// rode in the step of resident slot slot_map[b][hop mod map_ring].  Behind a restart inside the binding (RagStream::restart, hop_base): t0 counts
+// from the restart, the first 480 samples are the zeros of the restarted FIFO, and the hops are numbered on from hop_base -- the hops the
+// stream fired before the restart are never read again.  In bounds: hop_base >= 0 and k >= 0 where slot_map is read, so the index is in
+// [0, map_ring); the entry was written by the input half of the call that fired that hop, launched in front of this launch.
 static __global__ __launch_bounds__(256) void wrapr_post_kernel(const float* __restrict__ out24 /* [io_slots][B][240] */, const int B,
                                                                 const int* __restrict__ slot_map, const int map_ring, StreamState* __restrict__ st,
                                                                 const GainSeg* __restrict__ gain, const float* __restrict__ taps_all,
@@ -435,12 +448,13 @@ static __global__ __launch_bounds__(256) void wrapr_post_kernel(const float* __r
     }
   }
   const float* tl_ = stage_taps(d, taps, tid);
-  for (int i = tid; i < d.hist; i += 256) x[i] = hist[i];
+  if (r.restart) { for (int i = tid; i < d.hist; i += 256) x[i] = 0.0f; }
+  else for (int i = tid; i < d.hist; i += 256) x[i] = hist[i];
   for (int i = tid; i < d.n_in; i += 256) {
     const long long t = r.t0 + i;
     const long long k = t / kBlock - 1;
     const int off = (int)(t % kBlock);
-    x[d.hist + i] = (k < 0 || (off & 1)) ? 0.0f : out24[((size_t)slot_map[(size_t)b * map_ring + (int)(k % map_ring)] * B + b) * 240 + (off >> 1)];
+    x[d.hist + i] = (k < 0 || (off & 1)) ? 0.0f : out24[((size_t)slot_map[(size_t)b * map_ring + (int)((r.hop_base + k) % map_ring)] * B + b) * 240 + (off >> 1)];
   }
   __syncthreads();
   for (int o = tid; o < n; o += 256) {

@@ -179,6 +179,9 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *   (10) not rows of this table either: BeatriceBatch_ScanSilentBlocksBegin, ScanSilentBlocksEnd and ScanSilentBlocks are questions about the CALLER's
  *       device memory and work in every mode; BeatriceBatch_ScanBoundBlocks48k works exactly where the row "ConvertBlocks48kDevice(NULL, NULL)" says ok -- F --
  *       and is refused (-1) everywhere else.  No scan call drains anything, moves a clock, or changes a flag or setting of the batch.
+ *   (11) not rows of this table either, because they are settings: BeatriceBatch_SetStreamRateInFlight, RestartStreamInFlight and BoundStreamRate work
+ *       exactly where the row "ProcessBlocksRaggedDevice" says ok -- P -- and are refused (-1, the getter 0.0; nothing changes) everywhere else.  The six
+ *       calls of (9), BeatriceBatch_ResetStream and BeatriceBatch_ResetStreamInFlight behave in P as before: the six are refused, the two drain.
  *
  * Environment variables the library reads: BEATRICE_HIP_DEBUG (print HIP errors to stderr), BEATRICE_HIP_CUMASK ("lo-hi;lo-hi;..": CU masks
  * of the stage-pipelining streams), BEATRICE_HIP_HOP_GRAPH (the 1-stream calls replayed as hipGraphs), BEATRICE_HIP_NO_SPECULATION (no pitch hop beside
@@ -600,6 +603,38 @@ int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b);
  * refused until BeatriceBatch_ConfigureWrapperRates succeeds. */
 int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, float* d_out, int channels, int max_samples, int n_slots);
 int BeatriceBatch_ProcessBlocksRaggedDevice(BeatriceBatch* b, const int* n_samples);
+/* ONE stream's life cycle INSIDE that binding, without touching the others and without leaving the throughput mode: a caller's host changes
+ * its sample rate, a caller hangs up and another takes the slot.  The three calls work exactly where BeatriceBatch_ProcessBlocksRaggedDevice
+ * works (MODES, footnote 11: mode P) and are refused with -1 (the getter: 0.0) everywhere else, changing nothing.  They are settings, not
+ * mode entry points.  A call applies at the boundary in front of the next BeatriceBatch_ProcessBlocksRaggedDevice.
+ * BeatriceBatch_SetStreamRateInFlight is the reference's SetSampleRate (processor_core_2.cc:421-429) for that one stream: an equal rate
+ * returns 0 and does nothing; otherwise both resampler histories of the stream and its FIFO read as zeros from that call on, its two
+ * clocks, its FIFO fill and its 48 kHz sample count start over, both gains keep target and present value and ramp at the new rate; model
+ * state and settings are untouched.  BeatriceBatch_RestartStreamInFlight is the same restart, also at the present rate
+ * (host_sample_rate = 0.0; the reference: SetSampleRate(another rate), SetSampleRate(the rate)); with reset_model != 0 it also does what
+ * BeatriceBatch_ResetStreamInFlight does in plain tick mode -- the stream's next present step is the first step of a new stream, all four
+ * key/value blocks of its target speaker are installed at that step (set the new caller's voice first), steps already in the pipeline
+ * finish on the old state: the slot is turned over to a new caller.  A stream that then hands in n_samples = 0 starts over at the first
+ * step it takes part in.  BeatriceBatch_BoundStreamRate: the stream's rate in P (0.0: refused / bad argument); after the unbind
+ * BeatriceBatch_StreamRate reports it.
+ * NOTHING DRAINS: no call of the three synchronises, launches a tick or runs an output half -- BeatriceBatch_TicksLaunched and
+ * BeatriceBatch_ResidentBlocksOwed read the same before and after.  The blocks of earlier calls that are still owed come out
+ * BeatriceBatch_ResidentBlocksDelay() calls after their own call, with the old rate, the old taps and the old output histories, as if
+ * nothing had been asked; the restarted stream's first 480 inner samples behind the restart come back as zeros (the reference's zeroed
+ * FIFO), the hops it still has in the pipeline are never read; no bit of any other stream changes.  BeatriceBatch_Synchronize,
+ * BeatriceBatch_FlushResidentBlocks and the unbind work while a restart or a reset is waiting for the stream's next block.
+ * All or nothing.  -1 and no change: a stream out of range; a rate BeatriceBatch_SetStreamRate would refuse; a rate at which a block of
+ * min(max_samples, the rate's longest block) samples could fire more model hops per call than the binding's slot ring and slot map were
+ * sized for when it was made -- that size comes from the lowest rate among the streams at bind time, so BIND WHILE A STREAM OF THE LOWEST
+ * RATE YOU EXPECT IS CONFIGURED (and set its real rate with BeatriceBatch_SetStreamRateInFlight before the first call).  -2: HIP or
+ * allocation failure; nothing is committed.
+ * A rate no stream of the binding has had ALLOCATES (the rate's tap tables on the host, their place in the tap buffer, possibly a longer
+ * buffer; beatrice-vst_amd/csrc/wrapper_turnover_plan.h) and computes the tables: like BeatriceBatch_ScanSilentBlocksBegin it is not for an
+ * audio thread.  A rate the binding still holds -- a stream is on it, or was within the last ResidentBlocksDelay() + 1 calls -- costs a
+ * few stores. */
+int BeatriceBatch_SetStreamRateInFlight(BeatriceBatch* b, int stream, double host_sample_rate);
+int BeatriceBatch_RestartStreamInFlight(BeatriceBatch* b, int stream, double host_sample_rate /* 0.0: the present rate */, int reset_model);
+double BeatriceBatch_BoundStreamRate(const BeatriceBatch* b, int stream);
 
 /* Execution control: use an externally owned hipStream_t (e.g. the framework's current stream);
  * replay the per-hop kernel chain from a captured hipGraph (default on). */
