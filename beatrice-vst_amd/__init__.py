@@ -463,6 +463,10 @@ _BATCH = {
     "BeatriceBatch_StreamBlobBytes": (C.c_size_t, [_vp]),
     "BeatriceBatch_ExportStreams": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
     "BeatriceBatch_ImportStreams": (C.c_int, [_vp, C.c_int, _i32p, _vp, _i32p, C.c_int]),
+    "BeatriceBatch_StreamQuiescent": (C.c_int, [_vp, C.c_int]),
+    "BeatriceBatch_ExportStreamsInFlight": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
+    "BeatriceBatch_ImportStreamsInFlight": (C.c_int, [_vp, C.c_int, _i32p, _vp, _i32p, C.c_int]),
+    "BeatriceBatch_MoveStreamsInFlight": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, C.c_int]),
     "BeatriceBatch_ConvertFrames": (C.c_int, [_vp, _f32p, _f32p]),
     "BeatriceBatch_ConvertFramesDevice": (C.c_int, [_vp, _vp, _vp]),
     "BeatriceBatch_ConvertBlocks48k": (C.c_int, [_vp, _f32p, _f32p, C.c_int]),
@@ -633,6 +637,43 @@ class Batch:
         buf = C.create_string_buffer(bytes(blobs), max(1, len(blobs)))
         self._check(self.a.BeatriceBatch_ImportStreams(self.h, len(idx), iptr(idx), C.cast(buf, _vp),
                                                        None if em is None else iptr(em), 0 if em is None else len(em)))
+
+    def stream_quiescent(self, stream):
+        """In plain tick mode: True when no step the stream took part in is inside the pipeline (BeatriceBatch_StreamQuiescent),
+        which is when the in-flight calls below take it."""
+        rc = int(self.a.BeatriceBatch_StreamQuiescent(self.h, int(stream)))
+        if rc < 0:
+            raise RuntimeError("BeatriceBatch_StreamQuiescent failed: %d" % rc)
+        return rc == 1
+
+    def export_streams_in_flight(self, streams):
+        """export_streams' bytes of streams that are quiescent, without draining (BeatriceBatch_ExportStreamsInFlight): waits for the
+        ticks already enqueued and its own copy, launches no tick, changes nothing.  Not for an audio thread."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        buf = C.create_string_buffer(max(1, len(idx) * self.stream_blob_bytes()))
+        self._check(self.a.BeatriceBatch_ExportStreamsInFlight(self.h, len(idx), iptr(idx), C.cast(buf, _vp)))
+        return buf.raw[:len(idx) * self.stream_blob_bytes()]
+
+    def import_streams_in_flight(self, streams, blobs, entry_map=None):
+        """import_streams into streams that are quiescent, in front of the next tick and without waiting
+        (BeatriceBatch_ImportStreamsInFlight); each is turned to its own counter."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if len(blobs) != len(idx) * self.stream_blob_bytes():
+            raise ValueError("import_streams_in_flight: %d bytes for %d streams of %d bytes each" % (len(blobs), len(idx), self.stream_blob_bytes()))
+        em = None if entry_map is None else np.ascontiguousarray(entry_map, np.int32).reshape(-1)
+        buf = C.create_string_buffer(bytes(blobs), max(1, len(blobs)))
+        self._check(self.a.BeatriceBatch_ImportStreamsInFlight(self.h, len(idx), iptr(idx), C.cast(buf, _vp),
+                                                               None if em is None else iptr(em), 0 if em is None else len(em)))
+
+    def move_streams_in_flight(self, dst, streams, dst_streams, entry_map=None):
+        """Quiescent streams of this batch go on as dst_streams of `dst`, a batch on the same device, ring to ring on the device
+        (BeatriceBatch_MoveStreamsInFlight): no blob, no host wait.  This batch is unchanged."""
+        idx, to = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (streams, dst_streams))
+        if len(idx) != len(to):
+            raise ValueError("move_streams_in_flight: %d source streams, %d destination streams" % (len(idx), len(to)))
+        em = None if entry_map is None else np.ascontiguousarray(entry_map, np.int32).reshape(-1)
+        self._check(self.a.BeatriceBatch_MoveStreamsInFlight(self.h, dst.h, len(idx), iptr(idx), iptr(to),
+                                                             None if em is None else iptr(em), 0 if em is None else len(em)))
 
     def set_stream_rate(self, stream, rate):
         """One stream's SetSampleRate (BeatriceBatch_SetStreamRate): its resampler pair and FIFO restart at `rate`, its gains keep

@@ -26,6 +26,7 @@
 #include "beatrice_batch.h"
 #include "silent_scan_plan.h"
 #include "stream_blob.h"
+#include "stream_move_plan.h"
 #include "tick.hip.h"
 #include "wrapper.hip.h"
 #include "wrapper_blob.h"
@@ -170,6 +171,18 @@ struct BeatriceBatch {
     PinnedBuf<unsigned char> h_stage;
     DevBuf<unsigned char> d_stage;
   } sb;
+  // BeatriceBatch_StreamQuiescent / ExportStreamsInFlight / ImportStreamsInFlight / MoveStreamsInFlight (stream_move_plan.h): which streams
+  // have a step inside the tick pipeline (marked by tick_run, cleared at every drained point); the event behind an in-flight export's
+  // copy; the pinned staging of the in-flight imports, a ring of two CALLS (an entry holds all the blobs of its call and grows with it;
+  // its event: the call's last scatter has run); the two events of a move between batches on different streams -- the source batch's own
+  // marks what the move may read, the destination's what it has read
+  struct StreamMoves {
+    smove::Presence seen;
+    Event ev_export, ev_src, ev_dst;
+    static constexpr int kCalls = 2;
+    struct Staged { PinnedBuf<unsigned char> h; Event done; bool marked = false; } staged[kCalls];
+    long long imports = 0;
+  } mv;
   bool inflight = false;  // device-variant steps have been enqueued since the last synchronisation
   // staging for the host variant
   PinnedBuf<float> h_in, h_out;
@@ -1469,17 +1482,9 @@ long long BeatriceBatch_TicksLaunched(const BeatriceBatch* b) { return b && b->t
 // batch's one counter, tick_relevel has run), so a blob is "the stream before step `counter`", and the destination, which stands at a
 // counter of its own, turns every ring by the difference as it takes the blob in.
 namespace {
-bool blob_streams_ok(const BeatriceBatch* b, int n, const int* streams) {
-  if (n < 1 || n > b->B || !streams) return false;
-  std::vector<char> seen(b->B, 0);
-  for (int i = 0; i < n; ++i) {
-    if (streams[i] < 0 || streams[i] >= b->B || seen[streams[i]]) return false;
-    seen[streams[i]] = 1;
-  }
-  return true;
-}
-// the piece table (once per batch, the way tick_reset_prepare builds its ring table) and staging for min(n, 16) blobs
-bool blob_prepare(BeatriceBatch* b, int n) {
+bool blob_streams_ok(const BeatriceBatch* b, int n, const int* streams) { return smove::streams_ok(b->B, n, streams); }
+// the piece table (once per batch, the way tick_reset_prepare builds its ring table) ...
+bool blob_pieces(BeatriceBatch* b) {
   BeatriceBatch::StreamBlobs& sb = b->sb;
   const sblob::Layout& l = sb.layout;
   if (!sb.d_pieces) {
@@ -1500,6 +1505,13 @@ bool blob_prepare(BeatriceBatch* b, int n) {
       return false;
     sb.n_pieces = (int)pieces.size(); sb.d_pieces = std::move(d_pieces);
   }
+  return true;
+}
+// ... and staging for min(n, 16) blobs
+bool blob_prepare(BeatriceBatch* b, int n) {
+  if (!blob_pieces(b)) return false;
+  BeatriceBatch::StreamBlobs& sb = b->sb;
+  const sblob::Layout& l = sb.layout;
   const int want = std::min(n, sblob::kMaxRound);
   if (sb.cap < want) {
     PinnedBuf<unsigned char> h_stage;
@@ -1530,13 +1542,11 @@ static_assert(sblob::kIndices == 3 + B_NBLOCKS + 8 && std::is_trivially_copyable
 
 size_t BeatriceBatch_StreamBlobBytes(const BeatriceBatch* b) { return b && b->ok ? b->sb.layout.blob_bytes : 0; }
 
-int BeatriceBatch_ExportStreams(BeatriceBatch* b, int n, const int* streams, void* blobs) {
-  BATCH_OPEN(b);
-  if (!blob_streams_ok(b, n, streams) || !blobs) return -1;
-  // a reset that waits for the stream's next step has not happened yet: the rings still hold what it is to clear
-  if (b->tk.on && b->tk.any_reset_pending && (int)b->tk.reset_pending.size() == b->B)
-    for (int i = 0; i < n; ++i) if (b->tk.reset_pending[streams[i]]) return -3;
-  if (!blob_prepare(b, n) || !sync_all(b)) return -2;
+namespace {
+// The rounds of an export, drained or in flight: gather, copy down, the host part of every blob.  In flight nothing was drained: the
+// launch and the copy go behind the ticks already enqueued, the call waits for an event behind its own copy, and a blob's counter is
+// the stream's own (smove::own_counter) -- which at a drained point is the batch's.
+int export_rounds(BeatriceBatch* b, int n, const int* streams, void* blobs, bool in_flight) {
   BeatriceBatch::StreamBlobs& sb = b->sb;
   const sblob::Layout& l = sb.layout;
   unsigned char* out = static_cast<unsigned char*>(blobs);
@@ -1545,58 +1555,61 @@ int BeatriceBatch_ExportStreams(BeatriceBatch* b, int n, const int* streams, voi
     round.n = std::min(sb.cap, n - at);
     for (int j = 0; j < round.n; ++j) round.streams[j] = streams[at + j];
     if (!stream_gather(sb.d_pieces, sb.n_pieces, round, reinterpret_cast<float*>(sb.d_stage.get()), l.blob_bytes / sizeof(float), b->stream) ||
-        !hip_ok(hipMemcpyAsync(sb.h_stage, sb.d_stage, (size_t)round.n * l.blob_bytes, hipMemcpyDeviceToHost, b->stream), "blobs down") ||
-        !hip_ok(hipStreamSynchronize(b->stream), "stream gather"))
+        !hip_ok(hipMemcpyAsync(sb.h_stage, sb.d_stage, (size_t)round.n * l.blob_bytes, hipMemcpyDeviceToHost, b->stream), "blobs down"))
+      return -2;
+    if (in_flight ? !(hip_ok(hipEventRecord(b->mv.ev_export, b->stream), "export event") && hip_ok(hipEventSynchronize(b->mv.ev_export), "stream gather"))
+                  : !hip_ok(hipStreamSynchronize(b->stream), "stream gather"))
       return -2;
     for (int j = 0; j < round.n; ++j) {
       unsigned char* blob = sb.h_stage + (size_t)j * l.blob_bytes;
-      const StreamCfg& c = b->cfg[round.streams[j]];
+      const int s = round.streams[j];
+      const StreamCfg& c = b->cfg[s];
       int32_t idx[sblob::kIndices];
       blob_indices_of(c, idx);
       std::memset(blob, 0, l.off_state);
-      sblob::write_header(l, b->hop_host, blob);
+      sblob::write_header(l, smove::own_counter(in_flight && b->tk.ragged, b->tk.hop_s, s, b->hop_host), blob);
       std::memcpy(blob + l.off_indices, idx, sizeof(idx));
       std::memcpy(blob + l.off_cfg, &c, sizeof(c));
-      if (!sblob::engine_out(b->lottery[round.streams[j]], blob + l.off_engine)) return -2;
+      if (!sblob::engine_out(b->lottery[s], blob + l.off_engine)) return -2;
       std::memcpy(out + (size_t)(at + j) * l.blob_bytes, blob, l.blob_bytes);
     }
   }
   return 0;
 }
+}  // namespace
 
-int BeatriceBatch_ImportStreams(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
+int BeatriceBatch_ExportStreams(BeatriceBatch* b, int n, const int* streams, void* blobs) {
   BATCH_OPEN(b);
-  if (!blob_streams_ok(b, n, streams) || !blobs || n_map < 0 || (entry_map == nullptr) != (n_map == 0)) return -1;
-  BeatriceBatch::StreamBlobs& sb = b->sb;
-  const sblob::Layout& l = sb.layout;
-  const unsigned char* in = static_cast<const unsigned char*>(blobs);
-  struct Taken { StreamCfg cfg; std::mt19937 engine; int counter; };
-  std::vector<Taken> taken(n);
-  for (int i = 0; i < n; ++i) {   // every blob is looked at before anything is drained, uploaded or written
-    const unsigned char* blob = in + (size_t)i * l.blob_bytes;
-    int32_t idx[sblob::kIndices];
-    if (sblob::validate_header(l, blob, l.blob_bytes, B_HOP_WRAP, &taken[i].counter) != sblob::kOk ||
-        sblob::map_indices(l, blob, entry_map, n_map, b->n_speakers, b->max_speakers, idx) != sblob::kOk)
-      return -1;
-    std::memcpy(&taken[i].cfg, blob + l.off_cfg, sizeof(StreamCfg));
-    if (!blob_cfg_ok(taken[i].cfg) || !sblob::engine_in(blob + l.off_engine, &taken[i].engine)) return -1;
-    blob_indices_into(taken[i].cfg, idx);
-  }
+  if (!blob_streams_ok(b, n, streams) || !blobs) return -1;
+  // a reset that waits for the stream's next step has not happened yet: the rings still hold what it is to clear
+  if (b->tk.on && b->tk.any_reset_pending && (int)b->tk.reset_pending.size() == b->B)
+    for (int i = 0; i < n; ++i) if (b->tk.reset_pending[streams[i]]) return -3;
   if (!blob_prepare(b, n) || !sync_all(b)) return -2;
-  for (int at = 0; at < n; at += sb.cap) {
-    BlobRound round{};
-    round.n = std::min(sb.cap, n - at);
-    for (int j = 0; j < round.n; ++j) {
-      round.streams[j] = streams[at + j];
-      round.shift[j] = sblob::counter_shift(b->hop_host, taken[at + j].counter, B_HOP_WRAP);
-    }
-    std::memcpy(sb.h_stage, in + (size_t)at * l.blob_bytes, (size_t)round.n * l.blob_bytes);
-    if (!hip_ok(hipMemcpyAsync(sb.d_stage, sb.h_stage, (size_t)round.n * l.blob_bytes, hipMemcpyHostToDevice, b->stream), "blobs up") ||
-        !stream_scatter(sb.d_pieces, sb.n_pieces, round, reinterpret_cast<const float*>(sb.d_stage.get()), l.blob_bytes / sizeof(float), b->stream) ||
-        !hip_ok(hipStreamSynchronize(b->stream), "stream scatter"))
-      return -2;
+  return export_rounds(b, n, streams, blobs, false);
+}
+
+namespace {
+struct Taken { StreamCfg cfg; std::mt19937 engine; int counter; };
+// every blob is looked at before anything is drained, staged, uploaded or written
+bool blobs_take(const BeatriceBatch* b, int n, const void* blobs, const int* entry_map, int n_map, std::vector<Taken>* taken) {
+  const sblob::Layout& l = b->sb.layout;
+  const unsigned char* in = static_cast<const unsigned char*>(blobs);
+  taken->resize(n);
+  for (int i = 0; i < n; ++i) {
+    const unsigned char* blob = in + (size_t)i * l.blob_bytes;
+    Taken& t = (*taken)[i];
+    int32_t idx[sblob::kIndices];
+    if (sblob::validate_header(l, blob, l.blob_bytes, B_HOP_WRAP, &t.counter) != sblob::kOk ||
+        sblob::map_indices(l, blob, entry_map, n_map, b->n_speakers, b->max_speakers, idx) != sblob::kOk)
+      return false;
+    std::memcpy(&t.cfg, blob + l.off_cfg, sizeof(StreamCfg));
+    if (!blob_cfg_ok(t.cfg) || !sblob::engine_in(blob + l.off_engine, &t.engine)) return false;
+    blob_indices_into(t.cfg, idx);
   }
-  // the settings, as a change of every setting of the stream at once: the existing path takes them to the device with the next step
+  return true;
+}
+// the settings, as a change of every setting of the stream at once: the existing path takes them to the device with the next step
+void blobs_settle(BeatriceBatch* b, int n, const int* streams, const std::vector<Taken>& taken) {
   for (int i = 0; i < n; ++i) {
     const int s = streams[i];
     b->cfg[s] = taken[i].cfg;
@@ -1613,6 +1626,154 @@ int BeatriceBatch_ImportStreams(BeatriceBatch* b, int n, const int* streams, con
   for (const StreamCfg& c : b->cfg) if (c.kv_set_count < B_NBLOCKS) ++b->pending_kv;
   b->vq_dirty = true;
   for (int blk = 0; blk < B_NBLOCKS; ++blk) rebuild_tiles(b, blk);   // (marks every copy of the wave part for upload)
+}
+}  // namespace
+
+int BeatriceBatch_ImportStreams(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
+  BATCH_OPEN(b);
+  if (!blob_streams_ok(b, n, streams) || !blobs || n_map < 0 || (entry_map == nullptr) != (n_map == 0)) return -1;
+  BeatriceBatch::StreamBlobs& sb = b->sb;
+  const sblob::Layout& l = sb.layout;
+  const unsigned char* in = static_cast<const unsigned char*>(blobs);
+  std::vector<Taken> taken;
+  if (!blobs_take(b, n, blobs, entry_map, n_map, &taken)) return -1;
+  if (!blob_prepare(b, n) || !sync_all(b)) return -2;
+  for (int at = 0; at < n; at += sb.cap) {
+    BlobRound round{};
+    round.n = std::min(sb.cap, n - at);
+    for (int j = 0; j < round.n; ++j) {
+      round.streams[j] = streams[at + j];
+      round.shift[j] = sblob::counter_shift(b->hop_host, taken[at + j].counter, B_HOP_WRAP);
+    }
+    std::memcpy(sb.h_stage, in + (size_t)at * l.blob_bytes, (size_t)round.n * l.blob_bytes);
+    if (!hip_ok(hipMemcpyAsync(sb.d_stage, sb.h_stage, (size_t)round.n * l.blob_bytes, hipMemcpyHostToDevice, b->stream), "blobs up") ||
+        !stream_scatter(sb.d_pieces, sb.n_pieces, round, reinterpret_cast<const float*>(sb.d_stage.get()), l.blob_bytes / sizeof(float), b->stream) ||
+        !hip_ok(hipStreamSynchronize(b->stream), "stream scatter"))
+      return -2;
+  }
+  blobs_settle(b, n, streams, taken);
+  return 0;
+}
+
+// ---- the same between two batches that both go on ticking (beatrice_batch.h; the rules: stream_move_plan.h) --------------------------------
+// Nothing drains and no tick is launched: the streams named are at rest (no step of theirs is inside the pipeline), every launch enqueued
+// from here on skips their rows until they are fed again, so the gather, the scatter or the ring-to-ring move, enqueued on the batch's
+// stream between two ticks, touches state nobody else reads or writes.  Each stream is taken, and turned, at its OWN counter.
+namespace {
+struct MoveSide : smove::Side {   // one batch's part of a call
+  MoveSide(const BeatriceBatch* b, int n_, const int* streams_, bool pointers_ok_) {
+    plain_tick = modes::mode_of(flags_of(b)) == modes::Mode::D;
+    B = b->B; n = n_; streams = streams_; pointers_ok = pointers_ok_;
+  }
+};
+smove::Verdict move_at_rest(const BeatriceBatch* b, const smove::Side& s, bool is_source) {
+  const tick::State& k = b->tk;
+  const bool flags = is_source && k.any_reset_pending && (int)k.reset_pending.size() == b->B;   // (a destination's pending reset is cancelled, not refused)
+  return smove::at_rest(s, b->mv.seen, k.tick, k.plan.count(), flags ? k.reset_pending.data() : nullptr);
+}
+int move_own_counter(const BeatriceBatch* b, int s) { return smove::own_counter(b->tk.ragged, b->tk.hop_s, s, b->hop_host); }
+}  // namespace
+
+int BeatriceBatch_StreamQuiescent(const BeatriceBatch* b, int stream) {
+  if (!b || !b->ok || modes::mode_of(flags_of(b)) != modes::Mode::D || stream < 0 || stream >= b->B) return -1;
+  return b->mv.seen.quiescent(stream, b->tk.tick, b->tk.plan.count()) ? 1 : 0;
+}
+
+int BeatriceBatch_ExportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, void* blobs) {
+  BATCH_OPEN(b);
+  const MoveSide side(b, n, streams, blobs != nullptr);
+  if (smove::args(side) != smove::kGo) return -1;
+  if (move_at_rest(b, side, true) != smove::kGo) return -3;
+  if (!blob_prepare(b, n) || (!b->mv.ev_export && !b->mv.ev_export.create("export event"))) return -2;
+  return export_rounds(b, n, streams, blobs, true);
+}
+
+int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
+  BATCH_OPEN(b);
+  const MoveSide side(b, n, streams, blobs != nullptr && n_map >= 0 && (entry_map == nullptr) == (n_map == 0));
+  if (smove::args(side) != smove::kGo) return -1;
+  std::vector<Taken> taken;
+  if (!blobs_take(b, n, blobs, entry_map, n_map, &taken)) return -1;
+  if (move_at_rest(b, side, false) != smove::kGo) return -3;
+  if (!blob_prepare(b, n)) return -2;   // (the device staging of a round is the drained calls': everything that uses it is on the batch's stream, in order)
+  BeatriceBatch::StreamBlobs& sb = b->sb;
+  const sblob::Layout& l = sb.layout;
+  BeatriceBatch::StreamMoves::Staged& st = b->mv.staged[b->mv.imports % BeatriceBatch::StreamMoves::kCalls];
+  if (st.marked && !hip_ok(hipEventSynchronize(st.done), "import staging entry")) return -2;   // (the call before the last has not been scattered yet)
+  st.marked = false;
+  const size_t bytes = (size_t)n * l.blob_bytes;
+  if (st.h.size() < bytes) {
+    PinnedBuf<unsigned char> h;
+    if (!h.alloc(bytes, "import staging", false)) return -2;
+    st.h = std::move(h);
+  }
+  if (!st.done && !st.done.create("import staging event")) return -2;
+  std::memcpy(st.h, blobs, bytes);
+  for (int at = 0; at < n; at += sb.cap) {
+    BlobRound round{};
+    round.n = std::min(sb.cap, n - at);
+    for (int j = 0; j < round.n; ++j) {
+      round.streams[j] = streams[at + j];
+      round.shift[j] = smove::import_shift(move_own_counter(b, streams[at + j]), taken[at + j].counter, B_HOP_WRAP);
+    }
+    if (!hip_ok(hipMemcpyAsync(sb.d_stage, st.h + (size_t)at * l.blob_bytes, (size_t)round.n * l.blob_bytes, hipMemcpyHostToDevice, b->stream), "blobs up") ||
+        !stream_scatter(sb.d_pieces, sb.n_pieces, round, reinterpret_cast<const float*>(sb.d_stage.get()), l.blob_bytes / sizeof(float), b->stream))
+      return -2;
+  }
+  if (!hip_ok(hipEventRecord(st.done, b->stream), "import staging event")) return -2;
+  st.marked = true;
+  b->mv.imports += 1;
+  blobs_settle(b, n, streams, taken);
+  return 0;
+}
+
+int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
+                                      const int* entry_map, int n_map) {
+  if (!src || !dst || src == dst) return -1;
+  if (!src->ok || !dst->ok) return -2;
+  if (src->device != dst->device) return -1;
+  const DeviceScope dev_(dst->device);
+  const bool map_ok = n_map >= 0 && (entry_map == nullptr) == (n_map == 0);
+  const MoveSide from(src, n, src_streams, map_ok), to(dst, n, dst_streams, map_ok);
+  if (smove::args(from) != smove::kGo || smove::args(to) != smove::kGo || !sblob::same_layout(src->sb.layout, dst->sb.layout)) return -1;
+  // the settings part, host to host, with the checks the blob path makes
+  std::vector<Taken> taken(n);
+  for (int i = 0; i < n; ++i) {
+    int32_t idx[sblob::kIndices], mapped[sblob::kIndices];
+    taken[i].cfg = src->cfg[src_streams[i]];
+    taken[i].engine = src->lottery[src_streams[i]];
+    taken[i].counter = move_own_counter(src, src_streams[i]);
+    blob_indices_of(taken[i].cfg, idx);
+    if (sblob::map_index_list(idx, entry_map, n_map, dst->n_speakers, dst->max_speakers, mapped) != sblob::kOk || !blob_cfg_ok(taken[i].cfg)) return -1;
+    blob_indices_into(taken[i].cfg, mapped);
+  }
+  if (move_at_rest(src, from, true) != smove::kGo || move_at_rest(dst, to, false) != smove::kGo) return -3;
+  if (!blob_pieces(src) || !blob_pieces(dst) || src->sb.n_pieces != dst->sb.n_pieces) return -2;
+  // different streams: the move waits for the source's ticks enqueued so far, and whatever the source enqueues later -- a reset, an
+  // import or a present step of the slot -- waits for the move
+  const bool two_streams = src->stream != dst->stream;
+  if (two_streams) {
+    if ((!src->mv.ev_src && !src->mv.ev_src.create("move source event")) || (!dst->mv.ev_dst && !dst->mv.ev_dst.create("move destination event")) ||
+        !hip_ok(hipEventRecord(src->mv.ev_src, src->stream), "move source event") ||
+        !hip_ok(hipStreamWaitEvent(dst->stream, src->mv.ev_src, 0), "move waits for the source"))
+      return -2;
+  }
+  bool ok = true;
+  for (int at = 0; at < n && ok; at += sblob::kMaxRound) {
+    MoveRound round{};
+    round.n = std::min(sblob::kMaxRound, n - at);
+    for (int j = 0; j < round.n; ++j) {
+      round.src[j] = src_streams[at + j];
+      round.dst[j] = dst_streams[at + j];
+      round.shift[j] = smove::import_shift(move_own_counter(dst, dst_streams[at + j]), taken[at + j].counter, B_HOP_WRAP);
+    }
+    ok = stream_move(src->sb.d_pieces, dst->sb.d_pieces, dst->sb.n_pieces, round, dst->stream);
+  }
+  if (two_streams)   // (also behind a launch that failed: the source must never overtake what WAS enqueued)
+    ok = hip_ok(hipEventRecord(dst->mv.ev_dst, dst->stream), "move destination event") &&
+         hip_ok(hipStreamWaitEvent(src->stream, dst->mv.ev_dst, 0), "source waits for the move") && ok;
+  if (!ok) return -2;
+  blobs_settle(dst, n, dst_streams, taken);
   return 0;
 }
 

@@ -546,7 +546,7 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
       for (int s = 0; s < b->B; ++s) {
         const bool out = sr.any_next && sr.next[s];
         h[s] = out ? -1 : k.hop_s[s];
-        if (!out) k.hop_s[s] = hop_next(k.hop_s[s]);
+        if (!out) { k.hop_s[s] = hop_next(k.hop_s[s]); b->mv.seen.fed(s, k.tick); }   // (stream_move_plan.h: the stream has a step inside from this tick on)
       }
       for (int s = b->B; s < k.row; ++s) h[s] = -1;
       hv_upload = Copy{reinterpret_cast<unsigned char*>(k.d_hopv + (size_t)(u % kRing) * k.row), reinterpret_cast<const unsigned char*>(h), (int)(sizeof(int) * k.row)};
@@ -561,7 +561,9 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
         }
         k.any_reset_pending = left;
       }
-    } else if (k.any_reset_pending) {   // (the common counter: every stream takes part)
+    }
+    if (!k.ragged) b->mv.seen.fed_all(k.tick);   // (the common counter: every stream takes part)
+    if (!k.ragged && k.any_reset_pending) {
       for (int s = 0; s < b->B; ++s)
         if (k.reset_pending[s]) { k.resets.push_back(State::Travelling{s, b->hop_host, k.tick}); k.reset_pending[s] = 0; }
       k.any_reset_pending = false;
@@ -760,6 +762,7 @@ bool tick_drain(BeatriceBatch* b) {
     b->rb.jobs.pop_front();
   }
   if (ok && b->tk.on && b->tk.ragged) ok = tick_relevel(b);   // (nothing is in flight: back to one counter and the common launch)
+  if (ok && b->tk.on) b->mv.seen.drained();
   return ok;
 }
 int tick_enable(BeatriceBatch* b, bool on) {
@@ -815,6 +818,7 @@ int tick_enable(BeatriceBatch* b, bool on) {
     std::fill(b->entry_free_at.begin(), b->entry_free_at.end(), 0);   // (stamps of an earlier stay in tick mode: the pipeline is empty)
     k.resets.clear(); k.reset_pending.assign(b->B, 0); k.any_reset_pending = false; k.reset_launches = 0;
     k.ragged = false;
+    b->mv.seen.start(b->B);
     for (bool& r : k.step_ragged) r = false;
     for (long long& f : k.fed_step) f = -1;
     k.table_dirty = true;

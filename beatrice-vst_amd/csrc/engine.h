@@ -331,6 +331,10 @@ struct BlobPiece { float* base; unsigned stride, slot_floats; int m; unsigned lo
 struct BlobRound { int n; int streams[16]; int shift[16]; };
 bool stream_gather(const BlobPiece* d_pieces, int n_pieces, const BlobRound& round, float* d_staging, size_t blob_floats, hipStream_t stream);
 bool stream_scatter(const BlobPiece* d_pieces, int n_pieces, const BlobRound& round, const float* d_staging, size_t blob_floats, hipStream_t stream);
+// The same between two batches of one layout on one device, ring to ring (BeatriceBatch_MoveStreamsInFlight): stream src[j] of the
+// source's piece table becomes stream dst[j] of the destination's, turned by shift[j] as a scatter turns it.
+struct MoveRound { int n; int src[16]; int dst[16]; int shift[16]; };
+bool stream_move(const BlobPiece* d_src_pieces, const BlobPiece* d_dst_pieces, int n_pieces, const MoveRound& round, hipStream_t stream);
 
 // The shell's silent-block test on device-resident blocks (BeatriceBatch_ScanSilentBlocks*; silent_scan.hip, the geometry and the
 // bounds of its reads: silent_scan_plan.h).  d_flags[block] = 1 when every sample of the block's down-mix equals 0.0f; one launch.

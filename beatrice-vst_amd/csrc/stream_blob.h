@@ -122,10 +122,9 @@ inline Refusal validate_header(const Layout& l, const unsigned char* blob, size_
 
 // The blob's table indices through entry_map (index i becomes entry_map[i]; NULL, 0: kept, and bounded by the table's capacity
 // max_entries as BeatriceBatch_SetTargetSpeaker bounds them).  A mapped index must name one of the destination's n_speakers entries.
-inline Refusal map_indices(const Layout& l, const unsigned char* blob, const int* entry_map, int n_map, int n_speakers, int max_entries,
-                           int32_t* mapped /* [kIndices] */) {
-  int32_t idx[kIndices];
-  std::memcpy(idx, blob + l.off_indices, sizeof(idx));
+// (map_index_list: the same for indices that never were in a blob -- BeatriceBatch_MoveStreamsInFlight, settings host to host)
+inline Refusal map_index_list(const int32_t* idx /* [kIndices] */, const int* entry_map, int n_map, int n_speakers, int max_entries,
+                              int32_t* mapped /* [kIndices] */) {
   for (int i = 0; i < kIndices; ++i) {
     if (!entry_map) {
       if (idx[i] < 0 || idx[i] >= max_entries) return kIndexRange;
@@ -138,6 +137,17 @@ inline Refusal map_indices(const Layout& l, const unsigned char* blob, const int
     mapped[i] = to;
   }
   return kOk;
+}
+inline Refusal map_indices(const Layout& l, const unsigned char* blob, const int* entry_map, int n_map, int n_speakers, int max_entries,
+                           int32_t* mapped /* [kIndices] */) {
+  int32_t idx[kIndices];
+  std::memcpy(idx, blob + l.off_indices, sizeof(idx));
+  return map_index_list(idx, entry_map, n_map, n_speakers, max_entries, mapped);
+}
+// two batches whose blobs are interchangeable: what validate_header holds a blob's header against
+inline bool same_layout(const Layout& a, const Layout& b) {
+  return a.H == b.H && a.cfg_bytes == b.cfg_bytes && a.w48_bytes == b.w48_bytes && a.blob_bytes == b.blob_bytes && a.rings.size() == b.rings.size() &&
+         (a.rings.empty() || std::memcmp(a.rings.data(), b.rings.data(), sizeof(RingShape) * a.rings.size()) == 0);
 }
 
 // How far a ring of m slots turns between the source's counter and the destination's: slot j of the blob lands in slot

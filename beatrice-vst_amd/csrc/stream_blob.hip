@@ -9,6 +9,8 @@
 //            indexed by counter % m, so slot i of the blob belongs in slot (i + shift) % m (ring_rotate_kernel's move, kernels_misc.hip.h).
 //            Source and destination are different buffers, so the turn is folded into the destination index of a plain copy -- no
 //            register array of up to 64 slots per lane as the in-place rotation needs.
+//   move:    both at once between two batches on one device (BeatriceBatch_MoveStreamsInFlight): from the source batch's piece table
+//            straight into the destination's, turned the same way; no staging buffer.
 // 16-byte loads and stores wherever a piece's slot is a multiple of four words and both ends are aligned (every ring is: arenas pad rings
 // to 64 words, blobs pad pieces to 4); the previous bin and the wrapper's history (286 words per stream) go word by word.
 #include <hip/hip_runtime.h>
@@ -69,9 +71,46 @@ __global__ __launch_bounds__(kThreads) void stream_scatter_kernel(const BlobPiec
   }
 }
 
+// Ring to ring between two batches on one device (BeatriceBatch_MoveStreamsInFlight): gather and scatter in one, no blob between.  The
+// two piece tables are of one layout (the host holds sblob::same_layout before it launches), so piece i of both names the same ring with
+// the same slot size and slot count; only base and per-stream stride are each batch's own.  The turn goes into the destination slot as
+// above.
+__global__ __launch_bounds__(kThreads) void stream_move_kernel(const BlobPiece* __restrict__ src_pieces, const BlobPiece* __restrict__ dst_pieces,
+                                                               const MoveRound round) {
+  const BlobPiece ps = src_pieces[blockIdx.x], pd = dst_pieces[blockIdx.x];
+  const int j = blockIdx.y;
+  if (j >= round.n) return;
+  const float* src = ps.base + (size_t)round.src[j] * ps.stride;
+  float* dst = pd.base + (size_t)round.dst[j] * pd.stride;
+  const unsigned m = (unsigned)pd.m, turn = m > 1 ? (unsigned)round.shift[j] % m : 0u;
+  const unsigned n = pd.slot_floats * m, first = blockIdx.z * kThreads + threadIdx.x, step = kThreads * kSplit;
+  if ((pd.slot_floats & 3u) == 0 && aligned16(src, dst)) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    uint4* d4 = reinterpret_cast<uint4*>(dst);
+    const unsigned per = pd.slot_floats / 4;
+    for (unsigned i = first; i < n / 4; i += step) {
+      const unsigned slot = i / per, e = i - slot * per;
+      const unsigned to = slot + turn >= m ? slot + turn - m : slot + turn;
+      d4[to * per + e] = s4[i];
+    }
+  } else {   // (the previous bin, the 48 kHz wrapper's history)
+    for (unsigned i = first; i < n; i += step) {
+      const unsigned slot = i / pd.slot_floats, e = i - slot * pd.slot_floats;
+      const unsigned to = slot + turn >= m ? slot + turn - m : slot + turn;
+      dst[to * pd.slot_floats + e] = src[i];
+    }
+  }
+}
+
 bool round_ok(int n_pieces, const BlobRound& round) { return n_pieces >= 1 && round.n >= 1 && round.n <= 16; }
 
 }  // namespace
+
+bool stream_move(const BlobPiece* d_src_pieces, const BlobPiece* d_dst_pieces, int n_pieces, const MoveRound& round, hipStream_t stream) {
+  if (n_pieces < 1 || round.n < 1 || round.n > 16) return false;
+  hipLaunchKernelGGL(stream_move_kernel, dim3(n_pieces, round.n, kSplit), dim3(kThreads), 0, stream, d_src_pieces, d_dst_pieces, round);
+  return hip_ok(hipGetLastError(), "stream move launch");
+}
 
 bool stream_gather(const BlobPiece* d_pieces, int n_pieces, const BlobRound& round, float* d_staging, size_t blob_floats, hipStream_t stream) {
   if (!round_ok(n_pieces, round)) return false;

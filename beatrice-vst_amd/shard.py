@@ -186,7 +186,24 @@ def affine_speaker(rank, world, local_stream, n_speakers):
     return rank + world * (local_stream % mine)
 
 
-def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None, reset_source=False, with_wrapper=False):
+def _move_streams_in_flight(src_batch, src_streams, dst_batch, dst_streams, entry_map, reset_source):
+    """move_streams(in_flight=True): both batches are in plain tick mode and go on ticking; the streams named are quiescent
+    (Batch.stream_quiescent).  On one device the rings go from batch to batch on the device and nothing is returned; across
+    devices the in-flight blob pair carries them and the blobs are returned."""
+    a = src_batch.a
+    if a.BeatriceBatch_Device(src_batch.h) == dst_batch.a.BeatriceBatch_Device(dst_batch.h):
+        src_batch.move_streams_in_flight(dst_batch, src_streams, dst_streams, entry_map)
+        blobs = None
+    else:
+        blobs = src_batch.export_streams_in_flight(src_streams)
+        dst_batch.import_streams_in_flight(dst_streams, blobs, entry_map)
+    if reset_source:
+        for s in src_streams:
+            src_batch._check(a.BeatriceBatch_ResetStreamInFlight(src_batch.h, int(s)))
+    return blobs
+
+
+def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None, reset_source=False, with_wrapper=False, in_flight=False):
     """Stream src_streams[i] of src_batch goes on as stream dst_streams[i] of dst_batch, with its state and settings
     (Batch.export_streams / Batch.import_streams): its next step there is bit for bit the step it would have run in
     src_batch.  Both batches drain.  The two are batches of ONE process (any two GPUs of it: each call runs on its batch's
@@ -201,9 +218,17 @@ def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None,
     also restarts the source slots' wrappers.  Returns (blobs, wrapper_blobs).
 
     Between ranks the blob is plain bytes: export_streams on the rank that has the stream, broadcast_bytes (or a
-    point-to-point send of a uint8 tensor) to the rank that takes it, import_streams there."""
+    point-to-point send of a uint8 tensor) to the rank that takes it, import_streams there.
+
+    in_flight: neither batch drains (both in plain tick mode, the streams quiescent): the device-to-device call when both batches
+    live on one device (returns None), the in-flight blob pair otherwise (returns the blobs); reset_source then marks the source
+    slots with BeatriceBatch_ResetStreamInFlight.  The any-rate wrapper's state does not travel this way: with_wrapper is refused."""
     if len(src_streams) != len(dst_streams):
         raise ValueError("move_streams: %d source streams, %d destination streams" % (len(src_streams), len(dst_streams)))
+    if in_flight:
+        if with_wrapper:
+            raise ValueError("move_streams: in_flight=True moves no wrapper state (with_wrapper=True needs the drained path)")
+        return _move_streams_in_flight(src_batch, src_streams, dst_batch, dst_streams, entry_map, reset_source)
     blobs = src_batch.export_streams(src_streams)
     wrapper_blobs = src_batch.export_stream_wrappers(src_streams) if with_wrapper else None
     dst_batch.import_streams(dst_streams, blobs, entry_map)

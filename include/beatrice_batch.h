@@ -182,6 +182,10 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *   (11) not rows of this table either, because they are settings: BeatriceBatch_SetStreamRateInFlight, RestartStreamInFlight and BoundStreamRate work
  *       exactly where the row "ProcessBlocksRaggedDevice" says ok -- P -- and are refused (-1, the getter 0.0; nothing changes) everywhere else.  The six
  *       calls of (9), BeatriceBatch_ResetStream and BeatriceBatch_ResetStreamInFlight behave in P as before: the six are refused, the two drain.
+ *   (12) not rows of this table either, because they are settings: BeatriceBatch_StreamQuiescent, ExportStreamsInFlight, ImportStreamsInFlight and
+ *       MoveStreamsInFlight work in plain tick mode -- D, H = 1 / 2 / 4, with or without the silent-block rule -- and are refused (-1; nothing changes)
+ *       in A, B, C, E, F, G, P and S, where BeatriceBatch_ExportStreams / ImportStreams remain the way.  F and P keep wrapper state whose output halves
+ *       run a tick or `delay` calls later: a stream at rest in the ticks is not yet at rest there.  That second quiescence rule is not built.
  *
  * Environment variables the library reads: BEATRICE_HIP_DEBUG (print HIP errors to stderr), BEATRICE_HIP_CUMASK ("lo-hi;lo-hi;..": CU masks
  * of the stage-pipelining streams), BEATRICE_HIP_HOP_GRAPH (the 1-stream calls replayed as hipGraphs), BEATRICE_HIP_NO_SPECULATION (no pitch hop beside
@@ -381,6 +385,46 @@ size_t BeatriceBatch_StreamBlobBytes(const BeatriceBatch* b);   /* bytes of ONE 
 int BeatriceBatch_ExportStreams(BeatriceBatch* b, int n, const int* streams, void* blobs /* host, n * StreamBlobBytes(b) */);
 int BeatriceBatch_ImportStreams(BeatriceBatch* b, int n, const int* streams, const void* blobs /* host, n blobs */,
                                 const int* entry_map, int n_map /* NULL, 0: speaker-table indices are kept as they are */);
+
+/* The same move between batches that BOTH GO ON TICKING: nothing drains, no tick is launched, no other stream of either batch is
+ * disturbed.  MODES footnote (12): plain tick mode (D), H = 1, 2 or 4, with or without the silent-block rule; refused with -1 everywhere
+ * else, where the drained calls above remain the way.
+ * What makes it possible is that the stream is AT REST.  BeatriceBatch_StreamQuiescent(b, s) is 1 when no step stream s took part in is
+ * inside the pipeline: either it has taken part in no step since the last drained point (BeatriceBatch_Synchronize, entering tick
+ * mode), or at least BeatriceBatch_TickStages(b) ticks have been launched since, and counting, the tick that fed its last present step
+ * -- the stream sat out (BeatriceBatch_SetSilentStreams), or nothing was fed, for TickStages - 1 further ticks.  0 otherwise; -1 for a
+ * stream out of range or outside D.  Without the silent-block rule every stream takes part in every step, and streams are at rest only
+ * while the pipeline is empty.  A stream at rest stands at its OWN step counter, which lags the batch's by the steps it sat out.
+ * BeatriceBatch_ExportStreamsInFlight writes the SAME blobs as BeatriceBatch_ExportStreams (format, version word and
+ * BeatriceBatch_StreamBlobBytes unchanged; a blob of either export is taken by either import); the counter in a blob's header is the
+ * stream's own.  The gather and the copy to the host are enqueued on the batch's stream behind the ticks already enqueued, and the call
+ * waits for its own copy alone, on an event recorded behind it.  It therefore WAITS FOR THE TICKS IN FRONT OF IT: it is a scheduler's
+ * call, not one for an audio thread.  BeatriceBatch_TicksLaunched, every stream's counter and BeatriceBatch_ResidentBlocksOwed read the
+ * same before and after, and the source is unchanged: fed again, the stream goes on as if nothing had been asked.
+ * BeatriceBatch_ImportStreamsInFlight validates every blob exactly as BeatriceBatch_ImportStreams does, then enqueues the upload from
+ * pinned staging and the scatter in front of the next tick and returns WITHOUT waiting.  Staging is a ring of two calls: a third call
+ * waits only if the device has not yet run the first one's scatter.  Every ring with more than one slot is turned by (the DESTINATION
+ * STREAM's own counter - the blob's counter) mod its slot count; the destination stream's counter does not change.  Settings and lottery
+ * engine are replaced on the host and reach the device with the next step fed, like any setting changed between two ticks (a stream that
+ * brings the first or takes away the last use of the k-NN stage drains there, as BeatriceBatch_SetVQNumNeighbors does).  A
+ * BeatriceBatch_ResetStreamInFlight still waiting on the slot is cancelled.
+ * BeatriceBatch_MoveStreamsInFlight is both at once for two batches ON ONE DEVICE with the same hops per step and ring layout: one
+ * launch per 16 streams copies ring to ring, turned on the way; no staging buffer, no trip over the host link, no host wait.  The
+ * settings move host to host with the checks of the blob path.  If the batches run on different HIP streams the launch, on the
+ * destination's, waits for an event on the source's, and the source's stream waits for an event behind the launch, so that a later
+ * reset, import or present step of the source slot cannot overtake the read; with one shared stream (BeatriceBatch_SetStream) no event
+ * is needed.  The source is unchanged: BeatriceBatch_ResetStreamInFlight turns the slot over afterwards.
+ * All or nothing, and a refused call changes nothing (no launch, no staging, no clock, no flag), in this order.  -1: n < 1 or n > the
+ * batch's streams; a NULL pointer (entry_map NULL with n_map != 0 and the reverse); a stream out of range or named twice; a mode other
+ * than D; on import everything BeatriceBatch_ImportStreams refuses; for a move also src == dst, a NULL batch, different devices, hops
+ * per step or layouts.  -3: a stream named, source or destination, is not quiescent; on export and move also a source stream with a
+ * BeatriceBatch_ResetStreamInFlight pending that no step has taken yet.  -2: HIP or allocation failure. */
+int BeatriceBatch_StreamQuiescent(const BeatriceBatch* b, int stream);
+int BeatriceBatch_ExportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, void* blobs /* host, n * StreamBlobBytes(b) */);
+int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, const void* blobs /* host, n blobs */,
+                                        const int* entry_map, int n_map);
+int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
+                                      const int* entry_map, int n_map);
 
 /* One step (H hops, H = 1 unless created with BeatriceBatch_CreateBlock) for every stream.
  * Host variant: in [B][H*160] @16 kHz, out [B][H*240] @24 kHz, synchronous.
