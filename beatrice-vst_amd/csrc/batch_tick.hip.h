@@ -21,6 +21,7 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   using GruQ = typename O::GruQ; using GruP = typename O::GruP; using GruQ1 = typename O::GruQ1; using GruP1 = typename O::GruP1;
   using GruQm = typename O::GruQm; using GruPm = typename O::GruPm;
   State& k = b->tk;
+  if (sparse && !sparse_table_at(H)) { k.table_sparse_total = 0; return true; }   // (no tick of this H runs it: tick_run; its types are fuse::Absent)
   auto tb = std::make_unique<typename O::Builder>();
   const PhoneWeights& pw = b->phone_m->w;
   const PitchWeights& qw = b->pitch_m->w;
@@ -131,9 +132,7 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   //  64 speakers' codebooks in play.  At the end of the table, where round 2 had put it by its one-hop cost, it ENDED the launch: 256
   //  workgroups alone on the chip from 229 to 283 us of configs[3]'s tick, profiles/r06_notes.md section 3.  Present only while some stream has k > 0)
   { const VqArgs a{H, ps.raw, phone_vector_ring(ps), hp(Plan::VQ), ps.d_cbT, ps.d_cnorm, ps.d_vqk}; tb->template add<T_VQ>(LaunchInfo{"phone.vq", 0, 4.0 * B * H * 256}, a, dim3(B, 1), Plan::VQ, !ps.skip_vq, 9.0 * H, true); }
-  if (!pl.split_tail) {
-    TailArgs ta = tail_args(ww, ws); ta.hop = hp(pl.tail()); tb->template add<T_TAIL>(tail_info(ws), ta, dim3(B, 1), pl.tail(), keep(4), 41, true);
-  } else {
+  {
     // the tail as three stages, several streams per workgroup (tail_stages.hip.h); same weights, same state block
     tst::StageArgs t1{}, t2{}, t3{};
     t1.in = ws.ya2; t1.out = ws.ya3; t2.in = ws.ya3; t2.out = ws.ya4; t3.in = ws.ya4;
@@ -346,8 +345,8 @@ struct HostProf {
 //           scratch h1, xa, q, sc, o   nothing                       -- xa: the second half reads the step's own frames, the others are unused here
 //           ya1, yb1, yc1              before res1a, res1b, up2, spare
 //           ya2                        before the tail's first stage, spare
-//           tail                       its three parts (YB2 YC2 | YA3 YB3 YC3 | YA4 YB4 YC4) before the tail stage that owns them, whole
-//                                      (one stage with the fused tail: all three before it); the sub-steps' carried frames live in LDS
+//           tail                       its three parts (YB2 YC2 | YA3 YB3 YC3 | YA4 YB4 YC4) before the tail stage that owns them, whole;
+//                                      the sub-steps' carried frames live in LDS
 //           ya3, ya4                   nothing                       -- their two-frame histories are TS_YA3 / TS_YA4 of the tail block
 static bool tick_reset_prepare(BeatriceBatch* b) {
   using namespace tick;
@@ -384,7 +383,7 @@ static bool tick_reset_prepare(BeatriceBatch* b) {
     const int part[4] = {TS_YB2, TS_YA3, TS_YA4, TAIL_STATE_FLOATS};
     for (int i = 0; i < 3; ++i) {
       rings.push_back(ResetRing{ws.tail.base + part[i], (unsigned)TAIL_STATE_FLOATS, (unsigned)(part[i + 1] - part[i]), 1});
-      stage.push_back(pl.split_tail ? pl.tail() + i : pl.tail()); spare.push_back(0);
+      stage.push_back(pl.tail() + i); spare.push_back(0);
     }
     ++accounted;
   }
@@ -645,7 +644,7 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
   static const bool no_sparse = bhip::meas_env("BEATRICE_HIP_TICK_NO_SPARSE") != nullptr;   // A/B switch for measurements
   // (one hop per step only: at two hops per step it measured no difference, at four the half-size bodies cost 1 % of a 20-step run --
   //  5 196 against 5 138 us of launches, profiles/r05_notes.md)
-  const bool sparse = highest >= 0 && highest < Plan::BLK0 && !no_sparse && b->H == 1;
+  const bool sparse = highest >= 0 && highest < Plan::BLK0 && !no_sparse && sparse_table_at(b->H);
   int occupied = 0;
   for (int s = 0; s < p.n_stages; ++s) occupied += p.hop[s] >= 0 ? 1 : 0;
   if (!k.resets.empty() && !tick_reset_launch(b, st)) return false;   // (behind the prologue and the tick before, in front of this tick's launch)

@@ -112,6 +112,17 @@ static inline void launch(hipStream_t stream, const Part<Ops>&... parts) {
 // 256->256 linears of the conditioned blocks, say) is compiled into the launch once.
 template <class Op, int CAP>
 struct Many { using op = Op; static constexpr int cap = CAP; };
+// A body type that keeps its place in a type list whose tables never hold it: Op's argument block, grid() and info() (the host code
+// that names the type compiles as before), an EMPTY body, one wavefront and no LDS -- the table kernel compiles nothing of Op.  A body
+// inlined into the kernel costs every other body registers and scratch whether it runs or not (profiles/live_bodies_notes.md).
+template <class Op>
+struct Absent : Op {
+  using Args = typename Op::Args;
+  static constexpr int NTHR = 64;
+  static constexpr int LDS_FLOATS = 0;
+  __device__ static __forceinline__ void run(const Args&, int, int, float*) {}
+  template <bool RAG> __device__ static __forceinline__ void run_t(const Args&, int, int, float*) {}
+};
 struct Span { int first, gx, type, arg; };  // workgroups [first, next first) run body `type` with its argument block `arg`
 constexpr int kMaxSpans = 64;
 // (bits 16-23 of Span::arg: the body's pipeline stage, see StepPairs)

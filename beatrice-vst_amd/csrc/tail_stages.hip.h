@@ -123,9 +123,10 @@ struct Split {
   static constexpr int CT = POW2 ? 1 : NTL;
 };
 
-// B fragments of a layer for this wavefront, k-blocks [KB0, KB1).  A layer's fragments are fetched in two halves: the first
+// B fragments of a layer for this wavefront, k-blocks [KB0, KB1).  A layer's fragments are fetched in two parts: the first
 // before the PREVIOUS layer's MFMAs (latency hidden behind them), the second after them -- with 64 channels a layer's
-// fragments are 48 registers, and two whole layers' worth beside the accumulators and the A-operand pipeline spill.
+// fragments are 48 registers, and two whole layers' worth beside the accumulators and the A-operand pipeline spill
+// (so does a layer and a half: res_res_up_body's KBS).
 template <int K, int NOUT, int KB0 = 0, int KB1 = K / 16>
 __device__ __forceinline__ void fetch_b(const float* __restrict__ wpacked, float4 (&bf)[Split<NOUT>::CT][K / 16], int wave, int lane) {
   using SP = Split<NOUT>;
@@ -493,13 +494,19 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const 
   float* Y = X + buf_floats<C, T, S>();
   float* HIN = Y + buf_floats<C, T, S>();   // [S][2][C] raw
   float* HC = HIN + S * 2 * C;              // [S][1][C] activated
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hop = stepc::step(a.hop);
   if (hop < 0) return;
   const int b0 = g * S;
   const int n_rows = (a.B - b0 < S ? a.B - b0 : S) * T;
   int* shop = reinterpret_cast<int*>(lds + stage_lds<C, T, S, 1>() - 8);
   auto sub_step = [&](const int fb, const bool first, const bool last) {
+    // (the lane's constants are worked out again in every sub-step: held across the `#pragma unroll 1` loop below they -- and what
+    //  the compiler derives from them -- were spilled at the loop's head and reloaded inside the layers, and a reload waits vmcnt(0)
+    //  under the fragments and residuals in flight; the empty asm keeps the compiler from hoisting them back out.  T2 at four hops per
+    //  step: 11 spills -> 0, profiles/live_bodies_notes.md)
+    int tid = threadIdx.x;
+    if constexpr (NSUB > 1) asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wave = tid >> 6;
     float4 bfa[Split<C>::CT][3 * C / 16], bfb[Split<C>::CT][3 * C / 16], bfu[Split<NUP>::CT][2 * C / 16];
     TST_STAMP(0);
     fetch_b<3 * C, C>(a.w[0], bfa, wave, lane);
@@ -508,10 +515,13 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const 
     TST_STAMP(1);
     __syncthreads();
     TST_STAMP(2);
-    constexpr int KBR = 3 * C / 16, KBU = 2 * C / 16;
-    fetch_b<3 * C, C, 0, KBR / 2>(a.w[1], bfb, wave, lane);
+    // (KBS: the k-blocks of the second layer's fragments requested AHEAD of the first layer's MFMAs, the rest behind them.  A half at 32
+    //  channels; a third at 64, where a layer's fragments are 48 registers: with a half ahead T1 spilled 9 / 11 / 15 registers at
+    //  4 / 2 / 1 hops per step, 9 of the reloads inside layer()'s pass loop; with a third it spills none)
+    constexpr int KBR = 3 * C / 16, KBU = 2 * C / 16, KBS = C > 32 ? KBR / 3 : KBR / 2;
+    fetch_b<3 * C, C, 0, KBS>(a.w[1], bfb, wave, lane);
     two_res_layers<C, T, S, TS_B, TS_C, 1, RAG>(a, hop, b0, n_rows, X, Y, HC, bfa, bfb, wave, lane, tid,
-                                           [&] { fetch_b<3 * C, C, KBR / 2, KBR>(a.w[1], bfb, wave, lane); },
+                                           [&] { fetch_b<3 * C, C, KBS, KBR>(a.w[1], bfb, wave, lane); },
                                            [&] { fetch_b<2 * C, NUP, 0, KBU / 2>(a.w[2], bfu, wave, lane); }, shop, C > 32 ? HC + S * C : nullptr, fb, last);
     fetch_b<2 * C, NUP, KBU / 2, KBU>(a.w[2], bfu, wave, lane);
     // ---- transposed conv (polyphase k2): X -> the next stage's ring, frame t UPR + n / COUT, channel n % COUT
@@ -546,7 +556,7 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const 
 #pragma unroll 1
     for (int sub = 0; sub < NSUB; ++sub) sub_step(sub * T, sub == 0, sub == NSUB - 1);
   }
-  if (!IN_FROM_RING_HISTORY) hin_to_state<C, S, TS_IN, RAG>(a, HIN, b0, tid, shop);
+  if (!IN_FROM_RING_HISTORY) hin_to_state<C, S, TS_IN, RAG>(a, HIN, b0, threadIdx.x, shop);
   TST_STAMP(8);
 }
 

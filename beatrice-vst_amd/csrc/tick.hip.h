@@ -75,9 +75,12 @@ constexpr int kGruRt = 2, kMidRt = 2, kRbRt = 2, kP1Rt = kMidRt;   // row tiles 
 //  32 workgroups of 28 us end the launch later than 64 of 18 us: 3.45 -> 3.55 M frames/s at 256 streams)
 constexpr int kF3Rt = 1;
 
+// The sparse table exists at one hop per step only (batch_tick.hip.h tick_run: measured no gain at two hops, a loss at four)
+constexpr bool sparse_table_at(int H) { return H == 1; }
+
 enum BodyType {
   T_F1, T_FFT, T_F2, T_F3, T_F4, T_F5, T_P1, T_RB, T_P23, T_POUT, T_HEAD, T_OUT, T_COND, T_INP, T_UP1, T_RES1A, T_RES1B, T_UP2,
-  T_QGRU, T_PGRU, T_VQ, T_TAIL, T_TAIL1, T_TAIL2, T_TAIL3, T_BLKA1, T_BLKA2, T_BLKA4, T_BLKA8, T_BLKB, T_BLKBQ,
+  T_QGRU, T_PGRU, T_VQ, T_TAIL1, T_TAIL2, T_TAIL3, T_BLKA1, T_BLKA2, T_BLKA4, T_BLKA8, T_BLKB, T_BLKBQ,
   T_F4S, T_F5S, T_RBS, T_P1S, T_UP1S, T_TAIL1S, T_TAIL2S, T_QGRU1, T_PGRU1, T_QGRUM, T_PGRUM, T_COUNT
 };
 // The bodies of a tick with H hops per stage (H = 1: a step is one 10 ms hop of every stream; H = 2: two -- every stage then
@@ -106,12 +109,14 @@ struct Ops {
   // in half-size pieces -- one row tile per convolution workgroup (and half the streams per tail workgroup, unused: see tick_run).  A
   // partly filled launch lasts as long as its longest workgroup and has idle slots to spare, so shorter workgroups in larger
   // numbers are what it wants (in a full tick they cost ~3 %: twice the weight traffic per row, more prologues).  Same arithmetic,
-  // same rings: a tick may use either table.
-  using OpF4s = rc::ConvRowsOp<typename PL::F4, kRbCols, 1>;
-  using OpF5s = rc::ConvRowsOp<typename PL::F5, kRbCols, 1>;
-  using OpRBs = rc::ConvRowsOp<typename PL::RBL, kRbCols, 1>;
-  using OpP1s = rc::ConvRowsOp<typename QL1::P1, 0, 1>;
-  using OpUP1s = rc::ConvRowsOp<UP<256, 128, 5, H>, 128, 1>;
+  // same rings: a tick may use either table.  Where no sparse table is ever built (sparse_table_at) the types keep their places in
+  // the list as fuse::Absent: the table kernels of that H hold none of their code.
+  template <class Op> using Sparse = std::conditional_t<sparse_table_at(H), Op, fuse::Absent<Op>>;
+  using OpF4s = Sparse<rc::ConvRowsOp<typename PL::F4, kRbCols, 1>>;
+  using OpF5s = Sparse<rc::ConvRowsOp<typename PL::F5, kRbCols, 1>>;
+  using OpRBs = Sparse<rc::ConvRowsOp<typename PL::RBL, kRbCols, 1>>;
+  using OpP1s = Sparse<rc::ConvRowsOp<typename QL1::P1, 0, 1>>;
+  using OpUP1s = Sparse<rc::ConvRowsOp<UP<256, 128, 5, H>, 128, 1>>;
   // the tail's stages: streams per workgroup so that a workgroup holds the same number of rows at every H (80 / 240 / 480; H = 2: T2 160).
   // H = 4: a stream's 320 / 960 frames of a step do not fit the LDS -- T2 and T3 run the step as two sub-steps of two hops, one after
   // the other inside the workgroup, the layers' histories carried in LDS (tail_stages.hip.h prologue / carry_histories)
@@ -119,8 +124,8 @@ struct Ops {
   using T1 = tst::T1OpS<(H == 1 ? tst::kT1Streams : (H == 2 ? 2 : 1)), H>;
   using T2 = tst::T2OpS<(H == 1 ? tst::kT2Streams : 1), H, NSUB>;
   using T3 = tst::T3OpS<(H == 1 ? tst::kT3Streams : 1), H, NSUB>;
-  using T1s = tst::T1OpS<(H == 1 ? 2 : 1), H>;
-  using T2s = tst::T2OpS<(H == 1 ? 2 : 1), H, NSUB>;
+  using T1s = Sparse<tst::T1OpS<(H == 1 ? 2 : 1), H>>;
+  using T2s = Sparse<tst::T2OpS<(H == 1 ? 2 : 1), H, NSUB>>;
   // The GRUs: the column-split cell (fused_small.hip.h; 32 streams x 16 hidden units per workgroup, a weight fragment held in
   // registers).  Hop t of a step needs the whole state vector of hop t - 1: with several hops per step the cell of hop t PUBLISHES
   // its state as tagged granules and the cell of hop t + 1 -- another set of workgroups of the SAME launch and stage, later in
@@ -141,7 +146,7 @@ struct Ops {
       fuse::Many<OpP1, 1>, fuse::Many<OpRB, 4>, fuse::Many<OpP23, 2>, fuse::Many<OpPOUT, 1>, fuse::Many<HeadOp8, 1>,
       fuse::Many<OpOUT, 1>, fuse::Many<CondOp2, 1>, fuse::Many<OpINP, 1>, fuse::Many<OpUP1, 1>, fuse::Many<OpRES1A, 1>,
       fuse::Many<OpRES1B, 1>, fuse::Many<OpUP2, 1>, fuse::Many<GruQ, 1>, fuse::Many<GruP, 1>,
-      fuse::Many<Vq, 1>, fuse::Many<TailOp<H>, 1>, fuse::Many<T1, 1>, fuse::Many<T2, 1>, fuse::Many<T3, 1>, fuse::Many<rc::BlockAOp<1, H>, 1>, fuse::Many<rc::BlockAOp<2, H>, 1>,
+      fuse::Many<Vq, 1>, fuse::Many<T1, 1>, fuse::Many<T2, 1>, fuse::Many<T3, 1>, fuse::Many<rc::BlockAOp<1, H>, 1>, fuse::Many<rc::BlockAOp<2, H>, 1>,
       fuse::Many<rc::BlockAOp<4, H>, 1>, fuse::Many<rc::BlockAOp<8, H>, 1>, fuse::Many<rc::BlockBOpH<H>, 4>, fuse::Many<rc::BlockBqOpH<H>, 4>,
       fuse::Many<OpF4s, 1>, fuse::Many<OpF5s, 1>, fuse::Many<OpRBs, 4>, fuse::Many<OpP1s, 1>, fuse::Many<OpUP1s, 1>, fuse::Many<T1s, 1>, fuse::Many<T2s, 1>,
       fuse::Many<GruQ1, 1>, fuse::Many<GruP1, 1>, fuse::Many<GruQm, 2>, fuse::Many<GruPm, 2>>;
@@ -158,9 +163,9 @@ struct Plan {
   static constexpr int per_block = 2;  // stages per conditioned block
   int blk(int b) const { return BLK0 + per_block * b; }
   int up1() const { return blk(B_NBLOCKS); }
-  int tail() const { return up1() + 4; }   // first of the tail's stages (one with the fused body, three with tail_stages.hip.h)
-  bool split_tail = true;
-  int count() const { return tail() + (split_tail ? 3 : 1); }
+  int tail() const { return up1() + 4; }   // first of the tail's three stages (tail_stages.hip.h; the in-order chain's one-workgroup-per-stream
+                                           // tail, wave_tail.hip.h, is no body of a tick: it shares only the state block's layout)
+  int count() const { return tail() + 3; }
 };
 constexpr int kMaxHops = 4;   // hops per stage per tick the launch is built for (Ops<1>, Ops<2>, Ops<4>)
 static_assert(Plan::BLK0 + Plan::per_block * B_NBLOCKS + 7 <= kMaxStages && kMaxStages + 2 <= kRing && kMaxStages <= fuse::kMaxStepPairs, "stage bookkeeping");

@@ -15,19 +15,24 @@ __global__ __launch_bounds__(512, 4) void body_kernel(const typename Op::Args a)
   if ((int)threadIdx.x < Op::NTHR) Op::template run_t<false>(a, blockIdx.x, blockIdx.y, lds);
 }
 #define INST(H, NAME) template __global__ void body_kernel<typename tick::Ops<H>::NAME, H>(const typename tick::Ops<H>::NAME::Args)
-#define BOTH(NAME) INST(1, NAME); INST(2, NAME)
-BOTH(OpF2); BOTH(OpF3); BOTH(OpF4); BOTH(OpF5); BOTH(OpRB); BOTH(OpOUT); BOTH(OpP1); BOTH(OpP23); BOTH(OpPOUT); BOTH(OpINP);
-BOTH(OpUP1); BOTH(OpRES1A); BOTH(OpRES1B); BOTH(OpUP2); BOTH(T1); BOTH(T2); BOTH(T3); BOTH(GruQ); BOTH(GruP); BOTH(Vq);
-INST(2, GruQ1); INST(2, GruP1);
+#define EACH(NAME) INST(1, NAME); INST(2, NAME); INST(4, NAME)
+EACH(OpF2); EACH(OpF3); EACH(OpF4); EACH(OpF5); EACH(OpRB); EACH(OpOUT); EACH(OpP1); EACH(OpP23); EACH(OpPOUT); EACH(OpINP);
+EACH(OpUP1); EACH(OpRES1A); EACH(OpRES1B); EACH(OpUP2); EACH(T1); EACH(T2); EACH(T3); EACH(GruQ); EACH(GruP); EACH(Vq);
+INST(2, GruQ1); INST(2, GruP1); INST(4, GruQ1); INST(4, GruP1); INST(4, GruQm); INST(4, GruPm);   // the linked cells: last hop; middle hops
+// the sparse table's bodies (one hop per step only: tick::sparse_table_at)
+INST(1, OpF4s); INST(1, OpF5s); INST(1, OpRBs); INST(1, OpP1s); INST(1, OpUP1s); INST(1, T1s); INST(1, T2s);
 template __global__ void body_kernel<F1Op2, 0>(const F1Op2::Args);
 template __global__ void body_kernel<FftOp2, 0>(const FftOp2::Args);
 template __global__ void body_kernel<HeadOp8, 0>(const HeadOp8::Args);
 template __global__ void body_kernel<CondOp2, 0>(const CondOp2::Args);
-template __global__ void body_kernel<rc::BlockAOp<1, 1>, 0>(const rc::BlockAArgs);
-template __global__ void body_kernel<rc::BlockAOp<8, 1>, 0>(const rc::BlockAArgs);
-template __global__ void body_kernel<rc::BlockAOp<1, 2>, 0>(const rc::BlockAArgs);
-template __global__ void body_kernel<rc::BlockAOp<8, 2>, 0>(const rc::BlockAArgs);
-template __global__ void body_kernel<rc::BlockBOpH<1>, 0>(const rc::BlockBArgs);
-template __global__ void body_kernel<rc::BlockBOpH<2>, 0>(const rc::BlockBArgs);
-template __global__ void body_kernel<rc::BlockBqOpH<1>, 0>(const rc::BlockBqArgs);
-template __global__ void body_kernel<rc::BlockBqOpH<2>, 0>(const rc::BlockBqArgs);
+#define BLOCKS(H) \
+  template __global__ void body_kernel<rc::BlockAOp<1, H>, 0>(const rc::BlockAArgs); template __global__ void body_kernel<rc::BlockAOp<2, H>, 0>(const rc::BlockAArgs); \
+  template __global__ void body_kernel<rc::BlockAOp<4, H>, 0>(const rc::BlockAArgs); template __global__ void body_kernel<rc::BlockAOp<8, H>, 0>(const rc::BlockAArgs); \
+  template __global__ void body_kernel<rc::BlockBOpH<H>, 0>(const rc::BlockBArgs); template __global__ void body_kernel<rc::BlockBqOpH<H>, 0>(const rc::BlockBqArgs)
+BLOCKS(1); BLOCKS(2); BLOCKS(4);
+
+// ... and the six table kernels themselves (the launch's own: fuse::table_kernel_w at the tick's register budget, common and ragged)
+template <bool RAG, class... Ms>
+const void* table_kernel_of(const fuse::Table<Ms...>*) { return reinterpret_cast<const void*>(&fuse::table_kernel_w<4, RAG, Ms...>); }
+#define TABLES(H) template const void* table_kernel_of<false>(const tick::Ops<H>::Tab*); template const void* table_kernel_of<true>(const tick::Ops<H>::Tab*)
+TABLES(1); TABLES(2); TABLES(4);
