@@ -488,6 +488,11 @@ _BATCH = {
     "BeatriceBatch_SetStreamRateInFlight": (C.c_int, [_vp, C.c_int, C.c_double]),
     "BeatriceBatch_RestartStreamInFlight": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int]),
     "BeatriceBatch_BoundStreamRate": (C.c_double, [_vp, C.c_int]),
+    "BeatriceBatch_BoundStreamQuiescent": (C.c_int, [_vp, C.c_int]),
+    "BeatriceBatch_MoveBoundStreamsInFlight": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, C.c_int]),
+    "BeatriceBatch_ExportBoundStreamsInFlight": (C.c_int, [_vp, C.c_int, _i32p, _vp, _vp]),
+    "BeatriceBatch_ImportBoundStreamsInFlight": (C.c_int, [_vp, C.c_int, _i32p, _vp, _vp, _i32p, C.c_int]),
+    "BeatriceBatch_BoundWrapperBlobBytes": (C.c_size_t, [_vp]),
     "BeatriceBatch_Synchronize": (C.c_int, [_vp]),
     "BeatriceBatch_BindResidentIO": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "BeatriceBatch_SetStream": (C.c_int, [_vp, _vp]),
@@ -703,6 +708,52 @@ class Batch:
     def bound_stream_rate(self, stream):
         """The stream's host rate inside a binding with clocks per stream (0.0 anywhere else)."""
         return float(self.a.BeatriceBatch_BoundStreamRate(self.h, int(stream)))
+
+    def bound_stream_quiescent(self, stream):
+        """Inside a binding with clocks per stream: True when the stream is at rest by both rules -- no step of it inside the ticks, the
+        output half of every call it handed a block in launched (BeatriceBatch_BoundStreamQuiescent) -- which is when the three calls below
+        take it: after BeatriceBatch_ResidentBlocksDelay() calls it sat out."""
+        rc = int(self.a.BeatriceBatch_BoundStreamQuiescent(self.h, int(stream)))
+        if rc < 0:
+            raise RuntimeError("BeatriceBatch_BoundStreamQuiescent failed: %d" % rc)
+        return rc == 1
+
+    def bound_wrapper_blob_bytes(self):
+        """Bytes of one stream's wrapper blob inside a binding with clocks per stream (0 anywhere else)."""
+        return int(self.a.BeatriceBatch_BoundWrapperBlobBytes(self.h))
+
+    def move_bound_streams_in_flight(self, dst, streams, dst_streams, entry_map=None):
+        """Streams at rest in this binding go on as dst_streams of `dst`, a batch bound the same way on the same device, with model
+        state, settings, wrapper state, rate, clocks and gain ramps (BeatriceBatch_MoveBoundStreamsInFlight): no blob, no host wait, no
+        drain.  This batch is unchanged.  A rate `dst` does not hold allocates: not for an audio thread."""
+        idx, to = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (streams, dst_streams))
+        if len(idx) != len(to):
+            raise ValueError("move_bound_streams_in_flight: %d source streams, %d destination streams" % (len(idx), len(to)))
+        em = None if entry_map is None else np.ascontiguousarray(entry_map, np.int32).reshape(-1)
+        self._check(self.a.BeatriceBatch_MoveBoundStreamsInFlight(self.h, dst.h, len(idx), iptr(idx), iptr(to),
+                                                                  None if em is None else iptr(em), 0 if em is None else len(em)))
+
+    def export_bound_streams_in_flight(self, streams):
+        """(stream blobs, wrapper blobs) of streams at rest in this binding, without draining (BeatriceBatch_ExportBoundStreamsInFlight):
+        the bytes of export_streams and export_stream_wrappers.  Waits for its own copies; changes nothing."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        ns, nw = len(idx) * self.stream_blob_bytes(), len(idx) * self.bound_wrapper_blob_bytes()
+        sbuf, wbuf = C.create_string_buffer(max(1, ns)), C.create_string_buffer(max(1, nw))
+        self._check(self.a.BeatriceBatch_ExportBoundStreamsInFlight(self.h, len(idx), iptr(idx), C.cast(sbuf, _vp), C.cast(wbuf, _vp)))
+        return sbuf.raw[:ns], wbuf.raw[:nw]
+
+    def import_bound_streams_in_flight(self, streams, blobs, wrapper_blobs, entry_map=None):
+        """Blob pair i becomes stream streams[i] of this binding, in front of its next block and without waiting
+        (BeatriceBatch_ImportBoundStreamsInFlight); the blobs of either export, bound or in order."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if len(blobs) != len(idx) * self.stream_blob_bytes() or len(wrapper_blobs) != len(idx) * self.bound_wrapper_blob_bytes():
+            raise ValueError("import_bound_streams_in_flight: %d + %d bytes for %d streams of %d + %d bytes each" %
+                             (len(blobs), len(wrapper_blobs), len(idx), self.stream_blob_bytes(), self.bound_wrapper_blob_bytes()))
+        em = None if entry_map is None else np.ascontiguousarray(entry_map, np.int32).reshape(-1)
+        sbuf = C.create_string_buffer(bytes(blobs), max(1, len(blobs)))
+        wbuf = C.create_string_buffer(bytes(wrapper_blobs), max(1, len(wrapper_blobs)))
+        self._check(self.a.BeatriceBatch_ImportBoundStreamsInFlight(self.h, len(idx), iptr(idx), C.cast(sbuf, _vp), C.cast(wbuf, _vp),
+                                                                    None if em is None else iptr(em), 0 if em is None else len(em)))
 
     def wrapper_blob_bytes(self):
         """Bytes of one stream's wrapper blob (0 where export_stream_wrappers / import_stream_wrappers are refused)."""

@@ -23,6 +23,7 @@
 
 #include "abi_objects.h"
 #include "batch_modes.h"
+#include "bound_move_plan.h"
 #include "beatrice_batch.h"
 #include "silent_scan_plan.h"
 #include "stream_blob.h"
@@ -308,6 +309,12 @@ struct BeatriceBatch {
     PinnedBuf<unsigned char> h_blob_stage;
     DevBuf<unsigned char> d_blob_stage;
     int blob_cap = 0;
+    // the in-flight form of the two (BeatriceBatch_ExportBoundStreamsInFlight / ImportBoundStreamsInFlight): the event behind an export's
+    // copy; pinned staging of the imports, a ring of two CALLS as StreamMoves::Staged (the device staging is shared with the drained
+    // calls: everything that uses it is on the batch's stream, in order)
+    Event ev_bound_export;
+    StreamMoves::Staged bound_staged[StreamMoves::kCalls];
+    long long bound_imports = 0;
   } rw;
   // The any-rate wrapper around the tick pipeline (BeatriceBatch_BindResidentBlocks): host-rate blocks resident on the device,
   // the input half of the chain in front of the ticks, the output half `delay` calls later (wrapper.hip.h wrap_post_kernel)
@@ -347,6 +354,9 @@ struct BeatriceBatch {
     std::vector<int> hop_base_s;                             // [B] hops_s at the stream's last restart
     std::vector<unsigned char> restart_s;                    // [B] the restart has not travelled yet
     int hops_cap = 0;                                        // hops one stream may fire per call: what io_slots and slot_map were sized for
+    // BeatriceBatch_BoundStreamQuiescent / MoveBoundStreamsInFlight / ExportBoundStreamsInFlight / ImportBoundStreamsInFlight
+    // (bound_move_plan.h): every stream's last active call of the binding
+    bmove::Marks marks;
   } rb;
   // BeatriceBatch_ScanSilentBlocks* (silent_scan_plan.h, silent_scan.hip): the shell's test on blocks the caller keeps on the device.
   // Beside the batch, not of it: a stream of its own, a ring of kTickets staging entries -- the kernel's flags on the device, the pinned
@@ -1688,13 +1698,10 @@ int BeatriceBatch_ExportStreamsInFlight(BeatriceBatch* b, int n, const int* stre
   return export_rounds(b, n, streams, blobs, true);
 }
 
-int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
-  BATCH_OPEN(b);
-  const MoveSide side(b, n, streams, blobs != nullptr && n_map >= 0 && (entry_map == nullptr) == (n_map == 0));
-  if (smove::args(side) != smove::kGo) return -1;
-  std::vector<Taken> taken;
-  if (!blobs_take(b, n, blobs, entry_map, n_map, &taken)) return -1;
-  if (move_at_rest(b, side, false) != smove::kGo) return -3;
+namespace {
+// the rings of an in-flight import: the blobs into the call's pinned staging entry, up and scattered round by round on the batch's stream,
+// each stream turned to its own counter; nothing is waited for but the entry's previous user
+int import_rounds_in_flight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const std::vector<Taken>& taken) {
   if (!blob_prepare(b, n)) return -2;   // (the device staging of a round is the drained calls': everything that uses it is on the batch's stream, in order)
   BeatriceBatch::StreamBlobs& sb = b->sb;
   const sblob::Layout& l = sb.layout;
@@ -1723,34 +1730,45 @@ int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* stre
   if (!hip_ok(hipEventRecord(st.done, b->stream), "import staging event")) return -2;
   st.marked = true;
   b->mv.imports += 1;
+  return 0;
+}
+}  // namespace
+
+int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
+  BATCH_OPEN(b);
+  const MoveSide side(b, n, streams, blobs != nullptr && n_map >= 0 && (entry_map == nullptr) == (n_map == 0));
+  if (smove::args(side) != smove::kGo) return -1;
+  std::vector<Taken> taken;
+  if (!blobs_take(b, n, blobs, entry_map, n_map, &taken)) return -1;
+  if (move_at_rest(b, side, false) != smove::kGo) return -3;
+  const int rc = import_rounds_in_flight(b, n, streams, blobs, taken);
+  if (rc) return rc;
   blobs_settle(b, n, streams, taken);
   return 0;
 }
 
-int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
-                                      const int* entry_map, int n_map) {
-  if (!src || !dst || src == dst) return -1;
-  if (!src->ok || !dst->ok) return -2;
-  if (src->device != dst->device) return -1;
-  const DeviceScope dev_(dst->device);
-  const bool map_ok = n_map >= 0 && (entry_map == nullptr) == (n_map == 0);
-  const MoveSide from(src, n, src_streams, map_ok), to(dst, n, dst_streams, map_ok);
-  if (smove::args(from) != smove::kGo || smove::args(to) != smove::kGo || !sblob::same_layout(src->sb.layout, dst->sb.layout)) return -1;
-  // the settings part, host to host, with the checks the blob path makes
-  std::vector<Taken> taken(n);
+namespace {
+// the settings part of a move, host to host, with the checks the blob path makes
+bool move_take(const BeatriceBatch* src, const BeatriceBatch* dst, int n, const int* src_streams, const int* entry_map, int n_map, std::vector<Taken>* taken) {
+  taken->resize(n);
   for (int i = 0; i < n; ++i) {
+    Taken& t = (*taken)[i];
     int32_t idx[sblob::kIndices], mapped[sblob::kIndices];
-    taken[i].cfg = src->cfg[src_streams[i]];
-    taken[i].engine = src->lottery[src_streams[i]];
-    taken[i].counter = move_own_counter(src, src_streams[i]);
-    blob_indices_of(taken[i].cfg, idx);
-    if (sblob::map_index_list(idx, entry_map, n_map, dst->n_speakers, dst->max_speakers, mapped) != sblob::kOk || !blob_cfg_ok(taken[i].cfg)) return -1;
-    blob_indices_into(taken[i].cfg, mapped);
+    t.cfg = src->cfg[src_streams[i]];
+    t.engine = src->lottery[src_streams[i]];
+    t.counter = move_own_counter(src, src_streams[i]);
+    blob_indices_of(t.cfg, idx);
+    if (sblob::map_index_list(idx, entry_map, n_map, dst->n_speakers, dst->max_speakers, mapped) != sblob::kOk || !blob_cfg_ok(t.cfg)) return false;
+    blob_indices_into(t.cfg, mapped);
   }
-  if (move_at_rest(src, from, true) != smove::kGo || move_at_rest(dst, to, false) != smove::kGo) return -3;
+  return true;
+}
+// The rings from batch to batch on the destination's stream, and `also(ok)` -- what else the call enqueues there -- inside the same fence.
+// Different streams: the move waits for the source's launches enqueued so far, and whatever the source enqueues later -- a reset, an
+// import or a present step of the slot -- waits for the move.
+extern "C++" template <class F>
+int move_rings_fenced(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams, const std::vector<Taken>& taken, F also) {
   if (!blob_pieces(src) || !blob_pieces(dst) || src->sb.n_pieces != dst->sb.n_pieces) return -2;
-  // different streams: the move waits for the source's ticks enqueued so far, and whatever the source enqueues later -- a reset, an
-  // import or a present step of the slot -- waits for the move
   const bool two_streams = src->stream != dst->stream;
   if (two_streams) {
     if ((!src->mv.ev_src && !src->mv.ev_src.create("move source event")) || (!dst->mv.ev_dst && !dst->mv.ev_dst.create("move destination event")) ||
@@ -1769,10 +1787,28 @@ int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, in
     }
     ok = stream_move(src->sb.d_pieces, dst->sb.d_pieces, dst->sb.n_pieces, round, dst->stream);
   }
+  ok = also(ok);
   if (two_streams)   // (also behind a launch that failed: the source must never overtake what WAS enqueued)
     ok = hip_ok(hipEventRecord(dst->mv.ev_dst, dst->stream), "move destination event") &&
          hip_ok(hipStreamWaitEvent(src->stream, dst->mv.ev_dst, 0), "source waits for the move") && ok;
-  if (!ok) return -2;
+  return ok ? 0 : -2;
+}
+}  // namespace
+
+int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
+                                      const int* entry_map, int n_map) {
+  if (!src || !dst || src == dst) return -1;
+  if (!src->ok || !dst->ok) return -2;
+  if (src->device != dst->device) return -1;
+  const DeviceScope dev_(dst->device);
+  const bool map_ok = n_map >= 0 && (entry_map == nullptr) == (n_map == 0);
+  const MoveSide from(src, n, src_streams, map_ok), to(dst, n, dst_streams, map_ok);
+  if (smove::args(from) != smove::kGo || smove::args(to) != smove::kGo || !sblob::same_layout(src->sb.layout, dst->sb.layout)) return -1;
+  std::vector<Taken> taken;
+  if (!move_take(src, dst, n, src_streams, entry_map, n_map, &taken)) return -1;
+  if (move_at_rest(src, from, true) != smove::kGo || move_at_rest(dst, to, false) != smove::kGo) return -3;
+  const int rc = move_rings_fenced(src, dst, n, src_streams, dst_streams, taken, [](bool ok) { return ok; });
+  if (rc) return rc;
   blobs_settle(dst, n, dst_streams, taken);
   return 0;
 }

@@ -574,6 +574,7 @@ int BeatriceBatch_ProcessBlocksRagged(BeatriceBatch* b, const float* in, float* 
 // buffer of their own first, the device state is written next, the host's bookkeeping last.
 namespace {
 static_assert(sizeof(wrapn::StreamState) == wblob::kStateBytes && wblob::kFifo == wrapn::kBlock, "wrapper_blob.h restates the wrapper's state block");
+static_assert(offsetof(wrapn::StreamState, fifo) + sizeof(float) * wrapn::kBlock == sizeof(wrapn::StreamState), "bound_move.hip: the FIFO is the state's last member");
 bool rag_settings_allowed(const BeatriceBatch* b) { return modes::allowed(Entry::ProcessBlocksRagged, flags_of(b)); }
 // The batch's rate classes once every stream s runs at want[s]: the old classes still in use keep their order, the rates no stream has
 // had yet (`fresh`, configured by the caller) follow; classes no stream uses any more are gone.  Unchanged set: nothing is built.
@@ -943,6 +944,7 @@ static int rbr_step(BeatriceBatch* b, const int* n_samples) {
   for (int s = 0; s < B; ++s) {   // (the plan stands: the streams' sample and hop counts move)
     if (!rs[s].active) continue;
     r.restart_s[s] = 0;
+    r.marks.active(s, call);   // (bound_move_plan.h rule (b): the output half of this call is owed for the stream)
     r.t48_s[s] += rs[s].din.n_out;
     for (int c = 0; c < rs[s].n_chunks; ++c) { r.hops_s[s] += rs[s].fires[c]; fire_at[c] = fire_at[c] || rs[s].fires[c]; }
   }
@@ -1018,6 +1020,7 @@ int BeatriceBatch_BindResidentBlocksRagged(BeatriceBatch* b, const float* d_in, 
   r.hops_s.assign(B, 0);
   r.hop_base_s.assign(B, 0);
   r.restart_s.assign(B, 0);
+  r.marks.start(B);
   r.hops_cap = hops_per_call;
   // the classes as BeatriceBatch_ConfigureWrapperRates has just laid them out: from here on they keep index and place (wrapper_turnover_plan.h)
   BeatriceBatch::RaggedWrap& rw = b->rw;
@@ -1120,6 +1123,216 @@ int BeatriceBatch_RestartStreamInFlight(BeatriceBatch* b, int stream, double hos
 double BeatriceBatch_BoundStreamRate(const BeatriceBatch* b, int stream) {
   if (!b || !b->ok || !rbr_settings_allowed(b) || stream < 0 || stream >= b->B) return 0.0;
   return b->rw.rate(stream);
+}
+// ---- a bound stream from one such binding into another, or into the two blobs and back, nothing drained (beatrice_batch.h; every
+// decision: bound_move_plan.h; the kernels: bound_move.hip) ------------------------------------------------------------------------
+// The streams named are at rest by both rules, so the launches enqueued on the batch's stream from here on leave their wrapper state, their
+// slot-map entries and their cells of the resident slots alone until they are fed again.  The model rings go the way of the tick-mode
+// calls (move_rings_fenced / export_rounds / import_rounds_in_flight), each stream turned at its own counter; the wrapper state, the hop
+// the stream carries and the destination's slot-map entry by one more launch per round of 16; rate, clocks, gain clocks and the 48 kHz
+// sample count from host to host.  No tick is launched, no output half runs, nothing is waited for but an export's own copy.
+namespace {
+struct BoundSideOf : bmove::Side {
+  BoundSideOf(const BeatriceBatch* b, int n_, const int* streams_, bool pointers_ok_) {
+    bound_ragged = rbr_settings_allowed(b);
+    B = b->B; n = n_; streams = streams_; pointers_ok = pointers_ok_;
+  }
+};
+static bmove::Rest bound_rest(const BeatriceBatch* b, bool is_source) {
+  const tick::State& k = b->tk;
+  bmove::Rest r;
+  r.seen = &b->mv.seen; r.ticks = k.tick; r.stages = k.plan.count(); r.marks = &b->rb.marks;
+  r.oldest_owed = b->rb.jobs.empty() ? b->rb.calls : b->rb.jobs.front().call;
+  if (is_source) {   // (a destination's pending reset or restart is cancelled, not refused)
+    if (k.any_reset_pending && (int)k.reset_pending.size() == b->B) r.reset_pending = k.reset_pending.data();
+    r.restart_pending = b->rb.restart_s.data();
+  }
+  return r;
+}
+static BoundSide bound_side(BeatriceBatch* b) {
+  return BoundSide{reinterpret_cast<float*>(b->d_wrap.get()), b->rb.d_out24.get(), b->rb.d_map.get(), b->B, b->rb.io_slots, b->rb.map_ring};
+}
+static bmove::Item bound_source_item(const BeatriceBatch* b, int s) {
+  return bmove::source_item(s, b->rb.hops_s[s], b->rb.t48_s[s], b->rw.clk[s].fill, b->rb.map_ring);
+}
+static bmove::Item bound_dest_item(const BeatriceBatch* b, int t, int fill) {
+  return bmove::dest_item(t, b->rb.hops_s[t], fill, b->io_host, b->rb.io_slots, b->rb.map_ring);
+}
+// a stream's host side as it travels
+struct BoundTaken { double rate; wrapn::Clocks clk; wrapn::GainClock gain_in, gain_out; long long t48; };
+bool bound_rates_fit(const BeatriceBatch* b, const std::vector<BoundTaken>& w) {
+  for (const BoundTaken& t : w) if (!bmove::rate_fits(t.rate, b->rb.max_samples, b->rb.hops_cap)) return false;
+  return true;
+}
+// The destination acquires every stream's class as BeatriceBatch_SetStreamRateInFlight does (a rate no held class has is placed and goes
+// up: it may allocate) and joins it at once, so that the next placement's reap keeps it; the streams leave their old classes in
+// bound_commit.  -2: nothing is joined any more, no stream's class has changed.
+int bound_acquire(BeatriceBatch* b, const std::vector<BoundTaken>& w, std::vector<int>* cls) {
+  BeatriceBatch::RaggedWrap& rw = b->rw;
+  cls->assign(w.size(), -1);
+  for (size_t i = 0; i < w.size(); ++i) {
+    int c = rw.arena.find(w[i].rate);
+    if (c < 0) {
+      wrapn::RateClass fresh;
+      c = fresh.configure(w[i].rate) ? rbr_place(b, fresh) : -2;   // (cannot be refused here: bound_rates_fit has configured it)
+    }
+    if (c < 0) {
+      for (size_t j = 0; j < i; ++j) rw.arena.leave((*cls)[j], b->rb.calls);
+      return -2;
+    }
+    rw.arena.join(c, b->rb.calls);
+    (*cls)[i] = c;
+  }
+  return 0;
+}
+// the host's bookkeeping, last (nothing here fails)
+void bound_commit(BeatriceBatch* b, int n, const int* streams, const std::vector<BoundTaken>& w, const std::vector<int>& cls) {
+  BeatriceBatch::ResidentBlocks& r = b->rb;
+  BeatriceBatch::RaggedWrap& rw = b->rw;
+  for (int i = 0; i < n; ++i) {
+    const int t = streams[i];
+    rw.arena.leave(rw.cls[t], r.calls);
+    rw.cls[t] = cls[i];
+    rw.clk[t] = w[i].clk;
+    b->gain_in[t] = w[i].gain_in; b->gain_out[t] = w[i].gain_out;
+    r.hop_base_s[t] = bmove::hop_base(r.hops_s[t], w[i].t48, r.map_ring);
+    r.t48_s[t] = w[i].t48;
+    r.restart_s[t] = 0;   // (a restart still waiting for the slot's next block: the stream that arrives replaces what it would start over)
+  }
+}
+}  // namespace
+
+int BeatriceBatch_BoundStreamQuiescent(const BeatriceBatch* b, int stream) {
+  if (!b || !b->ok || !rbr_settings_allowed(b) || stream < 0 || stream >= b->B) return -1;
+  return bmove::quiescent(bound_rest(b, false), stream) ? 1 : 0;
+}
+size_t BeatriceBatch_BoundWrapperBlobBytes(const BeatriceBatch* b) { return b && b->ok && rbr_settings_allowed(b) ? wblob::kBlobBytes : 0; }
+
+int BeatriceBatch_MoveBoundStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
+                                           const int* entry_map, int n_map) {
+  if (!src || !dst || src == dst) return -1;
+  if (!src->ok || !dst->ok) return -2;
+  if (src->device != dst->device) return -1;
+  const DeviceScope dev_(dst->device);
+  const bool map_ok = n_map >= 0 && (entry_map == nullptr) == (n_map == 0);
+  const BoundSideOf from(src, n, src_streams, map_ok), to(dst, n, dst_streams, map_ok);
+  if (bmove::args(from) != bmove::kGo || bmove::args(to) != bmove::kGo || !sblob::same_layout(src->sb.layout, dst->sb.layout)) return -1;
+  std::vector<Taken> taken;
+  if (!move_take(src, dst, n, src_streams, entry_map, n_map, &taken)) return -1;
+  std::vector<BoundTaken> w(n);
+  for (int i = 0; i < n; ++i) {
+    const int s = src_streams[i];
+    w[i] = BoundTaken{src->rw.rate(s), src->rw.clk[s], src->gain_in[s], src->gain_out[s], src->rb.t48_s[s]};
+  }
+  if (!bound_rates_fit(dst, w)) return -1;
+  if (bmove::at_rest(from, bound_rest(src, true)) != bmove::kGo || bmove::at_rest(to, bound_rest(dst, false)) != bmove::kGo) return -3;
+  std::vector<int> cls;
+  if (bound_acquire(dst, w, &cls) != 0) return -2;
+  const int rc = move_rings_fenced(src, dst, n, src_streams, dst_streams, taken, [&](bool ok) {
+    for (int at = 0; at < n && ok; at += sblob::kMaxRound) {
+      BoundRound round{};
+      round.n = std::min(sblob::kMaxRound, n - at);
+      for (int j = 0; j < round.n; ++j) {
+        round.src[j] = bound_source_item(src, src_streams[at + j]);
+        round.dst[j] = bound_dest_item(dst, dst_streams[at + j], round.src[j].fill);
+      }
+      ok = bound_move(bound_side(src), bound_side(dst), round, dst->stream);
+    }
+    return ok;
+  });
+  if (rc) {
+    for (int c : cls) dst->rw.arena.leave(c, dst->rb.calls);
+    return rc;
+  }
+  bound_commit(dst, n, dst_streams, w, cls);
+  blobs_settle(dst, n, dst_streams, taken);
+  return 0;
+}
+
+int BeatriceBatch_ExportBoundStreamsInFlight(BeatriceBatch* b, int n, const int* streams, void* stream_blobs, void* wrapper_blobs) {
+  BATCH_OPEN(b);
+  const BoundSideOf side(b, n, streams, stream_blobs != nullptr && wrapper_blobs != nullptr);
+  if (bmove::args(side) != bmove::kGo) return -1;
+  if (bmove::at_rest(side, bound_rest(b, true)) != bmove::kGo) return -3;
+  BeatriceBatch::RaggedWrap& r = b->rw;
+  if (!blob_prepare(b, n) || !wblob_prepare(b, n) || (!b->mv.ev_export && !b->mv.ev_export.create("export event")) ||
+      (!r.ev_bound_export && !r.ev_bound_export.create("bound export event")))
+    return -2;
+  const int rc = export_rounds(b, n, streams, stream_blobs, true);
+  if (rc) return rc;
+  unsigned char* out = static_cast<unsigned char*>(wrapper_blobs);
+  for (int at = 0; at < n; at += r.blob_cap) {
+    BoundRound round{};
+    round.n = std::min(r.blob_cap, n - at);
+    for (int j = 0; j < round.n; ++j) round.src[j] = bound_source_item(b, streams[at + j]);
+    if (!bound_gather(bound_side(b), round, reinterpret_cast<float*>(r.d_blob_stage.get()), wblob::kBlobBytes / sizeof(float), wblob::kOffState / sizeof(float), b->stream) ||
+        !hip_ok(hipMemcpyAsync(r.h_blob_stage, r.d_blob_stage, (size_t)round.n * wblob::kBlobBytes, hipMemcpyDeviceToHost, b->stream), "bound wrapper blobs down") ||
+        !hip_ok(hipEventRecord(r.ev_bound_export, b->stream), "bound export event") || !hip_ok(hipEventSynchronize(r.ev_bound_export), "bound gather"))
+      return -2;
+    for (int j = 0; j < round.n; ++j) {
+      const int s = streams[at + j];
+      unsigned char* blob = r.h_blob_stage + (size_t)j * wblob::kBlobBytes;
+      const wrapn::Clocks& c = r.clk[s];
+      wblob::write_header(r.rate(s), c.phase_down, c.phase_up, c.fill, b->gain_in[s].target_db, b->gain_in[s].now_db,
+                          b->gain_out[s].target_db, b->gain_out[s].now_db, blob);
+      std::memcpy(out + (size_t)(at + j) * wblob::kBlobBytes, blob, wblob::kBlobBytes);
+    }
+  }
+  return 0;
+}
+
+int BeatriceBatch_ImportBoundStreamsInFlight(BeatriceBatch* b, int n, const int* streams, const void* stream_blobs, const void* wrapper_blobs,
+                                             const int* entry_map, int n_map) {
+  BATCH_OPEN(b);
+  const BoundSideOf side(b, n, streams, stream_blobs != nullptr && wrapper_blobs != nullptr && n_map >= 0 && (entry_map == nullptr) == (n_map == 0));
+  if (bmove::args(side) != bmove::kGo) return -1;
+  std::vector<Taken> taken;
+  if (!blobs_take(b, n, stream_blobs, entry_map, n_map, &taken)) return -1;
+  BeatriceBatch::RaggedWrap& r = b->rw;
+  const unsigned char* in = static_cast<const unsigned char*>(wrapper_blobs);
+  std::vector<BoundTaken> w(n);
+  for (int i = 0; i < n; ++i) {   // (what BeatriceBatch_ImportStreamWrappers refuses)
+    const unsigned char* blob = in + (size_t)i * wblob::kBlobBytes;
+    double rate = 0.0;
+    if (wblob::read_rate(blob, wblob::kBlobBytes, &rate) != wblob::kOk || !std::isfinite(rate)) return -1;
+    wrapn::RateClass probe;   // (the rate through RateClass::configure: its hi bounds the clocks)
+    wblob::Header h;
+    if (!probe.configure(rate) || wblob::validate(blob, wblob::kBlobBytes, probe.hi, &h) != wblob::kOk) return -1;
+    w[i] = BoundTaken{rate, wrapn::Clocks{h.phase_down, h.phase_up, h.fill}, wrapn::GainClock{h.in_target_db, h.in_now_db},
+                      wrapn::GainClock{h.out_target_db, h.out_now_db}, bmove::t48_of_blob(h.fill)};
+  }
+  if (!bound_rates_fit(b, w)) return -1;
+  if (bmove::at_rest(side, bound_rest(b, false)) != bmove::kGo) return -3;
+  if (!wblob_prepare(b, n)) return -2;
+  BeatriceBatch::StreamMoves::Staged& st = r.bound_staged[r.bound_imports % BeatriceBatch::StreamMoves::kCalls];
+  if (st.marked && !hip_ok(hipEventSynchronize(st.done), "bound import staging entry")) return -2;
+  st.marked = false;
+  const size_t bytes = (size_t)n * wblob::kBlobBytes;
+  if (st.h.size() < bytes) {
+    PinnedBuf<unsigned char> h;
+    if (!h.alloc(bytes, "bound import staging", false)) return -2;
+    st.h = std::move(h);
+  }
+  if (!st.done && !st.done.create("bound import staging event")) return -2;
+  std::vector<int> cls;
+  if (bound_acquire(b, w, &cls) != 0) return -2;
+  auto fail = [&]() { for (int c : cls) r.arena.leave(c, b->rb.calls); return -2; };
+  if (import_rounds_in_flight(b, n, streams, stream_blobs, taken) != 0) return fail();
+  std::memcpy(st.h, wrapper_blobs, bytes);
+  for (int at = 0; at < n; at += r.blob_cap) {
+    BoundRound round{};
+    round.n = std::min(r.blob_cap, n - at);
+    for (int j = 0; j < round.n; ++j) round.dst[j] = bound_dest_item(b, streams[at + j], w[at + j].clk.fill);
+    if (!hip_ok(hipMemcpyAsync(r.d_blob_stage, st.h + (size_t)at * wblob::kBlobBytes, (size_t)round.n * wblob::kBlobBytes, hipMemcpyHostToDevice, b->stream), "bound wrapper blobs up") ||
+        !bound_scatter(bound_side(b), round, reinterpret_cast<const float*>(r.d_blob_stage.get()), wblob::kBlobBytes / sizeof(float), wblob::kOffState / sizeof(float), b->stream))
+      return fail();
+  }
+  if (!hip_ok(hipEventRecord(st.done, b->stream), "bound import staging event")) return fail();
+  st.marked = true;
+  r.bound_imports += 1;
+  bound_commit(b, n, streams, w, cls);
+  blobs_settle(b, n, streams, taken);
+  return 0;
 }
 int BeatriceBatch_ResidentBlocksDelay(const BeatriceBatch* b) { return b && b->ok && b->rb.on ? b->rb.delay : -1; }
 int BeatriceBatch_ResidentBlocksDelayFor(const BeatriceBatch* b, int n) { return b && b->ok && b->wrap.ready && n >= 1 ? rb_delay(b, n) : -1; }

@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <vector>
 
+#include "bound_move_plan.h"
 #include "hip_owned.h"
 #include "kernels_misc.hip.h"
 #include "meas_env.h"
@@ -335,6 +336,17 @@ bool stream_scatter(const BlobPiece* d_pieces, int n_pieces, const BlobRound& ro
 // source's piece table becomes stream dst[j] of the destination's, turned by shift[j] as a scatter turns it.
 struct MoveRound { int n; int src[16]; int dst[16]; int shift[16]; };
 bool stream_move(const BlobPiece* d_src_pieces, const BlobPiece* d_dst_pieces, int n_pieces, const MoveRound& round, hipStream_t stream);
+
+// A bound stream's wrapper state between two bindings with clocks per stream (BeatriceBatch_MoveBoundStreamsInFlight / ExportBoundStreamsInFlight /
+// ImportBoundStreamsInFlight; bound_move.hip, every index: bound_move_plan.h).  A side = one binding's wrapn::StreamState rows (as words),
+// its ticks' resident output slots [io_slots][B][240] and its slot map [B][map_ring]; a round = up to 16 streams, one workgroup each.
+// move: state and carried hop from side to side.  gather / scatter: the same through wrapper blobs in a staging buffer (blob j, blob_floats
+// words each, its state at word state_off), in the in-order form of the FIFO.  false, nothing launched: an item outside its side.
+struct BoundSide { float* st; float* out24; int* slot_map; int B, io_slots, map_ring; };
+struct BoundRound { int n; bmove::Item src[16]; bmove::Item dst[16]; };
+bool bound_move(const BoundSide& src, const BoundSide& dst, const BoundRound& round, hipStream_t stream);
+bool bound_gather(const BoundSide& src, const BoundRound& round, float* d_staging, size_t blob_floats, size_t state_off, hipStream_t stream);
+bool bound_scatter(const BoundSide& dst, const BoundRound& round, const float* d_staging, size_t blob_floats, size_t state_off, hipStream_t stream);
 
 // The shell's silent-block test on device-resident blocks (BeatriceBatch_ScanSilentBlocks*; silent_scan.hip, the geometry and the
 // bounds of its reads: silent_scan_plan.h).  d_flags[block] = 1 when every sample of the block's down-mix equals 0.0f; one launch.

@@ -242,6 +242,27 @@ def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None,
     return (blobs, wrapper_blobs) if with_wrapper else blobs
 
 
+def move_bound_streams(src, streams, dst, dst_streams, entry_map=None, turn_over_source=False):
+    """Stream streams[i] of `src` goes on as stream dst_streams[i] of `dst` while BOTH batches stay bound with clocks per stream
+    (BeatriceBatch_BindResidentBlocksRagged) and neither drains: the streams named are at rest (Batch.bound_stream_quiescent), and the
+    stream's next block in `dst` is the block it would have got in `src` -- model state, settings, rate, resampler and FIFO state, gain
+    ramps.  On one device the state goes from batch to batch on the device and None is returned; across devices the in-flight blob pair
+    carries it and (blobs, wrapper_blobs) is returned.  turn_over_source: the source slots are turned over to new callers
+    (BeatriceBatch_RestartStreamInFlight(s, 0.0, 1)).  move_streams is the drained way, and the way of every other mode."""
+    if len(streams) != len(dst_streams):
+        raise ValueError("move_bound_streams: %d source streams, %d destination streams" % (len(streams), len(dst_streams)))
+    if src.a.BeatriceBatch_Device(src.h) == dst.a.BeatriceBatch_Device(dst.h):
+        src.move_bound_streams_in_flight(dst, streams, dst_streams, entry_map)
+        out = None
+    else:
+        out = src.export_bound_streams_in_flight(streams)
+        dst.import_bound_streams_in_flight(dst_streams, out[0], out[1], entry_map)
+    if turn_over_source:
+        for s in streams:
+            src._check(src.a.BeatriceBatch_RestartStreamInFlight(src.h, int(s), 0.0, 1))
+    return out
+
+
 def max_over_ranks(value, world, dist, torch, device):
     if world == 1:
         return value

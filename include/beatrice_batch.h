@@ -185,7 +185,11 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *   (12) not rows of this table either, because they are settings: BeatriceBatch_StreamQuiescent, ExportStreamsInFlight, ImportStreamsInFlight and
  *       MoveStreamsInFlight work in plain tick mode -- D, H = 1 / 2 / 4, with or without the silent-block rule -- and are refused (-1; nothing changes)
  *       in A, B, C, E, F, G, P and S, where BeatriceBatch_ExportStreams / ImportStreams remain the way.  F and P keep wrapper state whose output halves
- *       run a tick or `delay` calls later: a stream at rest in the ticks is not yet at rest there.  That second quiescence rule is not built.
+ *       run a tick or `delay` calls later: a stream at rest in the ticks is not yet at rest there.  P is served by the calls of (13), which hold that second
+ *       quiescence rule; F still is not.
+ *   (13) not rows of this table either, because they are settings: BeatriceBatch_BoundStreamQuiescent, MoveBoundStreamsInFlight, ExportBoundStreamsInFlight,
+ *       ImportBoundStreamsInFlight and BoundWrapperBlobBytes work exactly where the row "ProcessBlocksRaggedDevice" says ok -- P -- and are refused (-1, the
+ *       size 0; nothing changes) everywhere else, D included: there the calls of (12) are the way.
  *
  * Environment variables the library reads: BEATRICE_HIP_DEBUG (print HIP errors to stderr), BEATRICE_HIP_CUMASK ("lo-hi;lo-hi;..": CU masks
  * of the stage-pipelining streams), BEATRICE_HIP_HOP_GRAPH (the 1-stream calls replayed as hipGraphs), BEATRICE_HIP_NO_SPECULATION (no pitch hop beside
@@ -679,6 +683,46 @@ int BeatriceBatch_ProcessBlocksRaggedDevice(BeatriceBatch* b, const int* n_sampl
 int BeatriceBatch_SetStreamRateInFlight(BeatriceBatch* b, int stream, double host_sample_rate);
 int BeatriceBatch_RestartStreamInFlight(BeatriceBatch* b, int stream, double host_sample_rate /* 0.0: the present rate */, int reset_model);
 double BeatriceBatch_BoundStreamRate(const BeatriceBatch* b, int stream);
+/* A stream MOVES between two such bindings with everything it owns, and neither batch drains: what BeatriceBatch_MoveStreamsInFlight /
+ * ExportStreamsInFlight / ImportStreamsInFlight are to plain tick mode, for mode P (MODES, footnote 13; refused with -1, the size 0,
+ * everywhere else, D included).  Settings, not mode entry points.  The rules: beatrice-vst_amd/csrc/bound_move_plan.h.
+ * AT REST.  A bound stream owns more than its model state: its resampler histories and FIFO, and the output of its last fired model hop,
+ * which the output half of its NEXT block still reads.  It is at rest when (a) no step of it is inside the ticks and (b) the output half of
+ * every call it handed a block in has been launched -- which is the case once BeatriceBatch_ResidentBlocksDelay() calls have been made in
+ * which it sat out (n_samples[s] = 0), or behind BeatriceBatch_Synchronize.  BeatriceBatch_BoundStreamQuiescent: 1 / 0; -1 out of range
+ * or outside P.
+ * NOTHING DRAINS: no call of the five launches a tick, runs an output half or synchronises the batch; BeatriceBatch_TicksLaunched,
+ * BeatriceBatch_ResidentBlocksOwed, every other stream's clocks and BeatriceBatch_BoundStreamRate of every other stream read the same
+ * before and after.  The export waits for its own copies only, on an event.
+ * THE SOURCE IS UNCHANGED: fed again, the stream goes on as if nothing had been asked; turn the slot over with
+ * BeatriceBatch_RestartStreamInFlight(s, 0.0, 1).  THE DESTINATION SLOT CONTINUES THE STREAM: the next block handed in for destination
+ * stream t is, bit for bit, the block source stream s would have got next, whatever block lengths follow -- one reference wrapper per
+ * stream (reference src/common/resample.h:401-438).  What travels: the model rings, each turned at the stream's own counter; settings and
+ * the lottery engine, through entry_map as in BeatriceBatch_ImportStreams; the wrapper's filter histories and FIFO, the last hop's
+ * output, the rate, both resampler clocks and the FIFO fill; both gain clocks (target and present dB: a ramp in progress goes on); the
+ * 48 kHz sample count.  The destination's own hop numbering goes on.  A reset or restart still pending on a DESTINATION stream is
+ * cancelled.  The destination acquires the rate's class exactly as BeatriceBatch_SetStreamRateInFlight does: a rate it does not hold
+ * ALLOCATES -- not for an audio thread.
+ * The blobs are interchangeable tokens: stream blobs are those of BeatriceBatch_ExportStreams, wrapper blobs those of
+ * BeatriceBatch_ExportStreamWrappers (same format, same version, BoundWrapperBlobBytes == WrapperBlobBytes of an in-order batch); a blob
+ * of either export is taken by either import, bound or in order.  (A wrapper blob holds the FIFO fill, not the 48 kHz sample count: an
+ * imported stream counts from 480 + fill, which reads the same samples.)
+ * All or nothing, in this order.  -1 and no change: arguments (a NULL pointer, n < 1, a stream out of range or named twice, entry_map /
+ * n_map not paired); a batch outside P; a blob BeatriceBatch_ImportStreams or ImportStreamWrappers would refuse; for the move src == dst,
+ * two devices, another hops per step or ring layout; a rate the destination would refuse in BeatriceBatch_SetStreamRateInFlight (its
+ * blocks could fire more hops per call than the binding was sized for).  -3 and no change: a named stream, source or destination, is not
+ * at rest by both rules, or a SOURCE stream has a BeatriceBatch_ResetStreamInFlight or a restart pending that no block has taken.  Only
+ * then is anything allocated, staged or launched; -2: HIP or allocation failure.
+ * Two batches on two HIP streams are fenced by events as in BeatriceBatch_MoveStreamsInFlight; on one shared stream
+ * (BeatriceBatch_SetStream) no event is needed. */
+int BeatriceBatch_BoundStreamQuiescent(const BeatriceBatch* b, int stream);
+int BeatriceBatch_MoveBoundStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
+                                           const int* entry_map, int n_map);
+int BeatriceBatch_ExportBoundStreamsInFlight(BeatriceBatch* b, int n, const int* streams, void* stream_blobs /* n * StreamBlobBytes */,
+                                             void* wrapper_blobs /* n * BoundWrapperBlobBytes */);
+int BeatriceBatch_ImportBoundStreamsInFlight(BeatriceBatch* b, int n, const int* streams, const void* stream_blobs, const void* wrapper_blobs,
+                                             const int* entry_map, int n_map);
+size_t BeatriceBatch_BoundWrapperBlobBytes(const BeatriceBatch* b);
 
 /* Execution control: use an externally owned hipStream_t (e.g. the framework's current stream);
  * replay the per-hop kernel chain from a captured hipGraph (default on). */
