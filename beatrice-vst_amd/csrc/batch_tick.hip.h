@@ -51,7 +51,13 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   // publishes into link t, the last hop only polls.  A cell must find its predecessor's states published when it starts (it holds a
   // slot while it waits), so the hops sit far apart in dispatch order: hop 0 ahead of every other body, the later ones at the points
   // marked gru_at() below, each behind at least one more round of the launch's workgroups.
-  // (GruArgs::passes: two row groups per workgroup from 512 streams on; BEATRICE_HIP_GRU_PASSES overrides, for measurements)
+  // (GruArgs::passes, the column-split cells only -- both cells at one hop per step, hop 0 of the phone GRU at four: two row groups per workgroup from 512
+  //  streams on; BEATRICE_HIP_GRU_PASSES overrides, for measurements.  The rows cells stream their weights and ignore it)
+  // time of a rows cell's workgroup (us; the means of a full four-hop tick's timeline at 256 streams, profiles/gru_rows_notes.md
+  // section 6: phone 23.8 / 25.9, pitch 11.0 / 20.0 / 15.8 by hop): what two_halves balances on
+  // (two hops per step: no timeline taken; with the pitch cell at 17 the tick measured 109.1 -> 113.6 us against the parent, at 14
+  //  108.4 -> 107.2, section 5 of the notes: the halves' balance there is the one that 14 gives)
+  constexpr double kGruRowsCostP = 25, kGruRowsCostQ = H == 2 ? 14 : 17;
   static const int gru_passes_env = bhip::meas_env("BEATRICE_HIP_GRU_PASSES") ? std::atoi(bhip::meas_env("BEATRICE_HIP_GRU_PASSES")) : 0;
   const int gru_passes = gru_passes_env > 0 ? gru_passes_env : (B >= 512 ? 2 : 1);
   auto link_p = [&](int t) { return k.d_link_p + (size_t)t * B * 256; };
@@ -59,17 +65,17 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   auto add_pgru = [&](int t) {
     if constexpr (H > 1) {
       GruArgs g{ps.rb[3], ps.h, pw.gru_wih, pw.gru_whh, pw.gru_bih, pw.gru_bhh, hp(Plan::PGRU), B, t, t + 1 < H ? link_p(t) : nullptr, t > 0 ? link_p(t - 1) : nullptr, k.h_link_dead, gru_passes};
-      if (t == 0) tb->template add<T_PGRU>(GruP::info("phone.gru", g), g, GruP::grid(g), Plan::PGRU, keep(1), 19);
-      else if (t == H - 1) tb->template add<T_PGRU1>(GruP1::info("phone.gru", g), g, GruP1::grid(g), Plan::PGRU, keep(1), 19);
-      else if constexpr (H > 2) tb->template add<T_PGRUM>(GruPm::info("phone.gru", g), g, GruPm::grid(g), Plan::PGRU, keep(1), 19);
+      if (t == 0) tb->template add<T_PGRU>(GruP::info("phone.gru", g), g, GruP::grid(g), Plan::PGRU, keep(1), H == 2 ? kGruRowsCostP : 19);
+      else if (t == H - 1) tb->template add<T_PGRU1>(GruP1::info("phone.gru", g), g, GruP1::grid(g), Plan::PGRU, keep(1), kGruRowsCostP);
+      else if constexpr (H > 2) tb->template add<T_PGRUM>(GruPm::info("phone.gru", g), g, GruPm::grid(g), Plan::PGRU, keep(1), kGruRowsCostP);
     }
   };
   auto add_qgru = [&](int t) {
     if constexpr (H > 1) {
       GruArgs g{qs.p[2], qs.h, qw.gru_wih, qw.gru_whh, qw.gru_bih, qw.gru_bhh, hp(Plan::QGRU), B, t, t + 1 < H ? link_q(t) : nullptr, t > 0 ? link_q(t - 1) : nullptr, k.h_link_dead, gru_passes};
-      if (t == 0) tb->template add<T_QGRU>(GruQ::info("pitch.gru", g), g, GruQ::grid(g), Plan::QGRU, keep(1), 12);
-      else if (t == H - 1) tb->template add<T_QGRU1>(GruQ1::info("pitch.gru", g), g, GruQ1::grid(g), Plan::QGRU, keep(1), 12);
-      else if constexpr (H > 2) tb->template add<T_QGRUM>(GruQm::info("pitch.gru", g), g, GruQm::grid(g), Plan::QGRU, keep(1), 12);
+      if (t == 0) tb->template add<T_QGRU>(GruQ::info("pitch.gru", g), g, GruQ::grid(g), Plan::QGRU, keep(1), kGruRowsCostQ);
+      else if (t == H - 1) tb->template add<T_QGRU1>(GruQ1::info("pitch.gru", g), g, GruQ1::grid(g), Plan::QGRU, keep(1), kGruRowsCostQ);
+      else if constexpr (H > 2) tb->template add<T_QGRUM>(GruQm::info("pitch.gru", g), g, GruQm::grid(g), Plan::QGRU, keep(1), kGruRowsCostQ);
     }
   };
   // gru_at(point): the hops placed at insertion point 0 (behind the conditioned blocks), 1 (behind the tail), 2 / 3 (where the second

@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "conv_gemm.hip.h"
+#include "fused_small.hip.h"   // GruArgs, glink: the cell of the tick tables is a body of this file (gru_rows_body)
 #include "kernels_misc.hip.h"
 #include "ring.h"
 #include "spec_math.hip.h"
@@ -783,6 +784,168 @@ struct ConvRowsOp {
   static inline bhip::LaunchInfo info(const char* name, const ConvArgs& a) { return ConvOp<L, TileCfg<1, 1, 1, 2, 1>>::info(name, a); }
   __device__ static __forceinline__ void run(const ConvArgs& a, int bx, int by, float* lds) { conv_rows_body<L, COLS, RT>(a, bx, by, lds); }
   template <bool RAG> __device__ static __forceinline__ void run_t(const ConvArgs& a, int bx, int by, float* lds) { conv_rows_body<L, COLS, RT, RAG>(a, bx, by, lds); }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The GRU cell of the TICK TABLES: the arithmetic of gru_fused_body (fused_small.hip.h), operation for operation, in the shape of the
+// other GEMM bodies.  A workgroup holds RT row tiles of 16 streams x 8 / RT column tiles of 16 hidden units (RT = 2: 32 streams x 64
+// hidden units, a cell of 256 streams x 256 units is 32 workgroups where the column-split cell has 128, each of which gathered the
+// same two [32][256] tiles for a sixteenth of the columns); wavefront w owns column tile w % (8 / RT) of row tile w / (8 / RT) for all
+// three gates, so the two wavefronts of a SIMD (w, w + 4) read the same weight fragments.  x and h sit in LDS as k-permuted tiles
+// [16 RT][IN + 8] and [16 RT][H + 8] (kpos, lds_kblock).  Order: the x chains' prologue fragments are requested, then x (which does not
+// depend on the link) and h (ring, or the granules of the hop before) are gathered behind them, ONE barrier, then the two reductions
+// through mma_segment_rt<1, 3, K / 16> -- x . Wih for the three gates, then h . Whh into three more accumulators: every sum one
+// k-ascending chain from zero over K <= 256 (MODEL_SPEC 2.2), the weights in the layout the column-split cell reads (column tile
+// (gate H + j0) / 16 + tile).  The six sums of a lane's four hidden units of one row meet IN REGISTERS: no gate block in LDS, no
+// second barrier; sigmoid2 on {r, z} of an element as before, tanh2 on two real elements (elementwise: the same bits).
+// LINK as in gru_fused_body; GruArgs::passes has no meaning here (the weights stream past every workgroup).
+template <int IN, int H, int RT> constexpr int gru_rows_lds() { return 16 * RT * (IN + 8) + 16 * RT * (H + 8); }
+template <int IN, int H, bool RAG = false, int LINK = 0, int RT = 2>
+__device__ __forceinline__ void gru_rows_body(const GruArgs& a, const int bx, const int by, float* __restrict__ lds) {
+  constexpr int XS = IN + 8, HS = H + 8, ROWS = 16 * RT, CT = NWAVE / RT;
+  constexpr int NPX = ROWS * (IN / 4) / NTHR, NPH = ROWS * (H / 4) / NTHR;   // 16-byte pieces per thread
+  static_assert(RT == 1 || RT == 2, "row tiles");
+  static_assert(NWAVE % (4 * RT) == 0, "piece_of: wave-loads w and w + NWAVE i hold the same rows (the gather takes a thread's row once)");
+  static_assert(IN % 64 == 0 && H % 64 == 0 && H % (16 * CT) == 0 && NPX >= 1 && NPH >= 1 && (XS / 4) % 16 == 2 && (HS / 4) % 16 == 2, "cell shape");
+  float* xs = lds;
+  float* hs = lds + ROWS * XS;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hop = __builtin_amdgcn_readfirstlane(stepc::step(a.hop));   // (uniform: the ring positions below are scalar arithmetic)
+  if (hop < 0) return;
+  const bool rag = stepc::rag_t<RAG>();   // (ragged step: every row at its stream's own counter, -1 = the stream sits the step out)
+  // (the common ring positions once, as scalars: the division behind `hop % m` runs on the vector pipe, and its operands would otherwise
+  //  stay in vector registers across both reductions for the state's store)
+  const int px = __builtin_amdgcn_readfirstlane(ring_pos(a.x, hop)), ph = __builtin_amdgcn_readfirstlane(ring_pos(a.h, hop));
+  asm volatile("" : : "s"(px), "s"(ph));   // (both HERE: left alone the second division sinks into the reductions and its operand is spilled)
+  const int b0 = bx * ROWS;
+  const int tile = by * CT + wave % CT, rt = wave / CT;
+  WStream wx[3], wh[3];
+#pragma unroll
+  for (int g = 0; g < 3; ++g) {
+    wx[g] = WStream::make(reinterpret_cast<const float4*>(a.wih) + (size_t)(g * (H / 16) + tile) * (IN / 16) * 64, lane);
+    wh[g] = WStream::make(reinterpret_cast<const float4*>(a.whh) + (size_t)(g * (H / 16) + tile) * (H / 16) * 64, lane);
+  }
+  // both tiles, gathered behind the x chains' prologue fragments (NoGather above): wave-load wave + 8 i of piece_of -- ONE row per
+  // thread, pieces 16 columns-of-four apart
+  auto gather = [&] {
+    int r, q0;
+    piece_of<4 * RT>(wave, lane, &r, &q0);
+    const int b = b0 + r;
+    const int hr = b < a.B ? (rag ? stepc::hopv[b] : hop) : -1;   // an absent row: zeros in both tiles
+    float4 vx[NPX], vh[NPH];
+    {
+      const float* xb = as_global(a.x.base);
+      const unsigned xi = ring_index(a.x, b, rag ? ring_pos(a.x, hr) : px, a.t);
+#pragma unroll
+      for (int i = 0; i < NPX; ++i) {
+        int ri, q;
+        piece_of<4 * RT>(wave + NWAVE * i, lane, &ri, &q);
+        vx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (hr >= 0) vx[i] = *reinterpret_cast<const float4*>(xb + (xi + 4u * (unsigned)q));
+      }
+    }
+    if constexpr ((LINK & 2) != 0) {   // the state the cell of the hop before published in THIS launch
+      const unsigned long long* gp = a.link_in + (size_t)b * H;
+      unsigned long long gv[NPH][4];
+#pragma unroll
+      for (int i = 0; i < NPH; ++i) {
+        int ri, q;
+        piece_of<4 * RT>(wave + NWAVE * i, lane, &ri, &q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[i][j] = hr >= 0 ? __hip_atomic_load(gp + 4 * q + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+      }
+#pragma unroll
+      for (int i = 0; i < NPX; ++i) {
+        int ri, q;
+        piece_of<4 * RT>(wave + NWAVE * i, lane, &ri, &q);
+        store_perm4(xs + r * XS, 4 * q, vx[i].x, vx[i].y, vx[i].z, vx[i].w);
+      }
+#pragma unroll
+      for (int i = 0; i < NPH; ++i) {
+        int ri, q;
+        piece_of<4 * RT>(wave + NWAVE * i, lane, &ri, &q);
+        float f[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          f[j] = hr < 0 ? 0.0f : ((int)(gv[i][j] >> 32) == hop + 1 ? __uint_as_float((unsigned)gv[i][j]) : glink::acquire(gp + 4 * q + j, hop + 1, a.link_dead));
+        store_perm4(hs + r * HS, 4 * q, f[0], f[1], f[2], f[3]);
+      }
+    } else {
+      const float* hb = as_global(a.h.base);
+      const unsigned hi = ring_index(a.h, b, rag ? ring_pos(a.h, hr) : ph, a.t - 1);
+#pragma unroll
+      for (int i = 0; i < NPH; ++i) {
+        int ri, q;
+        piece_of<4 * RT>(wave + NWAVE * i, lane, &ri, &q);
+        vh[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (hr >= 0) vh[i] = *reinterpret_cast<const float4*>(hb + (hi + 4u * (unsigned)q));
+      }
+#pragma unroll
+      for (int i = 0; i < NPX; ++i) {
+        int ri, q;
+        piece_of<4 * RT>(wave + NWAVE * i, lane, &ri, &q);
+        store_perm4(xs + r * XS, 4 * q, vx[i].x, vx[i].y, vx[i].z, vx[i].w);
+      }
+#pragma unroll
+      for (int i = 0; i < NPH; ++i) {
+        int ri, q;
+        piece_of<4 * RT>(wave + NWAVE * i, lane, &ri, &q);
+        store_perm4(hs + r * HS, 4 * q, vh[i].x, vh[i].y, vh[i].z, vh[i].w);
+      }
+    }
+    __syncthreads();   // (every thread of the workgroup comes through here: the only early return is the uniform one above)
+  };
+  f32x4 ax[1][3], ah[1][3];
+#pragma unroll
+  for (int g = 0; g < 3; ++g) { ax[0][g] = f32x4{0.f, 0.f, 0.f, 0.f}; ah[0][g] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  const int row = 16 * rt + (lane & 15);
+  mma_segment_rt<1, 3, IN / 16>(ax, xs + row * XS + lane_koff(lane), 0, wx, gather);
+  mma_segment_rt<1, 3, H / 16>(ah, hs + row * HS + lane_koff(lane), 0, wh);
+  // the gates: this lane's hidden units n0 .. n0 + 3 of row `row` (lane constants worked out here, not held across the loops)
+  const int b = b0 + row;
+  const int hr = b < a.B ? (rag ? stepc::hopv[b] : hop) : -1;
+  if (hr < 0) return;   // (an absent row neither writes state nor publishes; no barrier follows)
+  const int n0 = 16 * tile + 4 * (lane >> 4);
+  float bi[3][4], bh[3][4];
+#pragma unroll
+  for (int g = 0; g < 3; ++g) {
+    const float4 vi = *reinterpret_cast<const float4*>(a.bih + g * H + n0), vh = *reinterpret_cast<const float4*>(a.bhh + g * H + n0);
+    bi[g][0] = vi.x; bi[g][1] = vi.y; bi[g][2] = vi.z; bi[g][3] = vi.w;
+    bh[g][0] = vh.x; bh[g][1] = vh.y; bh[g][2] = vh.z; bh[g][3] = vh.w;
+  }
+  const float* hprev = hs + row * HS + kpos(n0);   // the previous state of these four units: elements KSTEP apart
+  float zz[4], pre[4], nn[4], hv[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float gi_r = ax[0][0][e] + bi[0][e], gi_z = ax[0][1][e] + bi[1][e], gi_n = ax[0][2][e] + bi[2][e];
+    const float gh_r = ah[0][0][e] + bh[0][e], gh_z = ah[0][1][e] + bh[1][e], gh_n = ah[0][2][e] + bh[2][e];
+    const bsp::f32x2 rz = bsp::sigmoid2(bsp::f32x2{gi_r + gh_r, gi_z + gh_z});   // (packed forms, spec_math.hip.h: the same bits)
+    zz[e] = rz.y;
+    pre[e] = bsp::fma(rz.x, gh_n, gi_n);
+  }
+  {
+    const bsp::f32x2 t0 = bsp::tanh2(bsp::f32x2{pre[0], pre[1]}), t1 = bsp::tanh2(bsp::f32x2{pre[2], pre[3]});
+    nn[0] = t0.x; nn[1] = t0.y; nn[2] = t1.x; nn[3] = t1.y;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) hv[e] = bsp::fma(zz[e], hprev[KSTEP * e] - nn[e], nn[e]);
+  *reinterpret_cast<float4*>(ring_frame(a.h, b, rag ? ring_pos(a.h, hr) : ph, a.t) + n0) = make_float4(hv[0], hv[1], hv[2], hv[3]);
+  if constexpr ((LINK & 1) != 0) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) glink::publish(a.link_out + (size_t)b * H + n0 + e, hv[e], hop + 1);
+  }
+}
+template <int IN, int H, int LINK = 0, int RT = 2>
+struct GruRowsOp {
+  using Args = GruArgs;
+  static constexpr int NTHR = rc::NTHR;
+  static constexpr int LDS_FLOATS = gru_rows_lds<IN, H, RT>();
+  static inline dim3 grid(const GruArgs& a) { return dim3((a.B + 16 * RT - 1) / (16 * RT), H / (16 * (NWAVE / RT))); }
+  static inline bhip::LaunchInfo info(const char* name, const GruArgs& a) {
+    return bhip::LaunchInfo{name, 2.0 * a.B * (IN + H) * 3.0 * H, 4.0 * ((IN + H) * 3.0 * H + a.B * (IN + 2.0 * H))};
+  }
+  __device__ static __forceinline__ void run(const GruArgs& a, int bx, int by, float* lds) { gru_rows_body<IN, H, false, LINK, RT>(a, bx, by, lds); }
+  template <bool RAG> __device__ static __forceinline__ void run_t(const GruArgs& a, int bx, int by, float* lds) { gru_rows_body<IN, H, RAG, LINK, RT>(a, bx, by, lds); }
 };
 
 // a body type that is never added to a table (keeps the type lists of the tick launch the same length at every hops-per-step)

@@ -70,7 +70,7 @@ using namespace wave_layers;
 // (Measured at 256 / 1024 streams: one row tile, full width 3.18 / 3.83 M frames/s; the three long
 //  layers as 32 rows x 128 columns 3.27 / 3.85; every conv_rows body with two row tiles 3.29 / 3.98)
 constexpr int kRbCols = 128;   // column slab of the three long layers (f4, f5, rb)
-constexpr int kGruRt = 2, kMidRt = 2, kRbRt = 2, kP1Rt = kMidRt;   // row tiles of 16 per workgroup
+constexpr int kMidRt = 2, kRbRt = 2, kP1Rt = kMidRt;   // row tiles of 16 per workgroup
 // (phone.f3 with ONE row tile: it runs in the launch's second round, where short workgroups matter more than traffic --
 //  32 workgroups of 28 us end the launch later than 64 of 18 us: 3.45 -> 3.55 M frames/s at 256 streams)
 constexpr int kF3Rt = 1;
@@ -126,19 +126,24 @@ struct Ops {
   using T3 = tst::T3OpS<(H == 1 ? tst::kT3Streams : 1), H, NSUB>;
   using T1s = Sparse<tst::T1OpS<(H == 1 ? 2 : 1), H>>;
   using T2s = Sparse<tst::T2OpS<(H == 1 ? 2 : 1), H, NSUB>>;
-  // The GRUs: the column-split cell (fused_small.hip.h; 32 streams x 16 hidden units per workgroup, a weight fragment held in
-  // registers).  Hop t of a step needs the whole state vector of hop t - 1: with several hops per step the cell of hop t PUBLISHES
+  // The GRUs: the rows cell (rowchain.hip.h gru_rows_body; 32 streams x 64 hidden units per workgroup, all three gates of a column
+  // tile in one wavefront, the weights streamed).  Hop t of a step needs the whole state vector of hop t - 1: with several hops per step the cell of hop t PUBLISHES
   // its state as tagged granules and the cell of hop t + 1 -- another set of workgroups of the SAME launch and stage, later in
   // dispatch order (tick_build_table) -- polls them (GruArgs::link_*): the one place where workgroups of a tick wait for each other.
   // GruQ / GruP: hop 0 (publishes when H > 1); GruQm / GruPm: hops 1 .. H - 2 (poll and publish; H = 4: two of each, every link
   // its own granule array); GruQ1 / GruP1: the last hop (polls)
   static_assert(H <= 4, "link arrays: tick::State");
-  using GruQ = GruOp<128, 128, kGruRt, (H > 1 ? 1 : 0)>;
-  using GruP = GruOp<256, 256, kGruRt, (H > 1 ? 1 : 0)>;
-  using GruQ1 = std::conditional_t<H == 1, rc::NopOp, GruOp<128, 128, kGruRt, 2>>;
-  using GruP1 = std::conditional_t<H == 1, rc::NopOp, GruOp<256, 256, kGruRt, 2>>;
-  using GruQm = std::conditional_t<H <= 2, rc::NopOp, GruOp<128, 128, kGruRt, 3>>;
-  using GruPm = std::conditional_t<H <= 2, rc::NopOp, GruOp<256, 256, kGruRt, 3>>;
+  // (one hop per step: both cells stay column-split -- there the cells sit at the END of the dispatch order, and 16-32 workgroups of
+  //  17-25 us end the launch later than 64-128 of 9-12 us: 61.8 -> 68.9 us per tick at 256 streams, profiles/gru_rows_notes.md section 5)
+  using GruQ = std::conditional_t<H == 1, GruOp<128, 128, 2, 0>, rc::GruRowsOp<128, 128, 1>>;
+  // (the phone cell of HOP 0 at four hops per step stays the column-split cell, fused_small.hip.h: with the rows cell in this place of
+  //  the type list the common four-hop kernel comes out at 18 VGPR spills -- one more, in the tail's T1 -- and that kernel is pinned
+  //  to 17, tests/test_cpu_tick_kernel_resources.py; profiles/gru_rows_notes.md)
+  using GruP = std::conditional_t<H == 2, rc::GruRowsOp<256, 256, 1>, GruOp<256, 256, 2, (H > 1 ? 1 : 0)>>;
+  using GruQ1 = std::conditional_t<H == 1, rc::NopOp, rc::GruRowsOp<128, 128, 2>>;
+  using GruP1 = std::conditional_t<H == 1, rc::NopOp, rc::GruRowsOp<256, 256, 2>>;
+  using GruQm = std::conditional_t<H <= 2, rc::NopOp, rc::GruRowsOp<128, 128, 3>>;
+  using GruPm = std::conditional_t<H <= 2, rc::NopOp, rc::GruRowsOp<256, 256, 3>>;
   using Vq = std::conditional_t<H == 1, VqOp, VqRowsOp<H>>;   // (several hops: a stream's rows in one workgroup, the codebook read once)
   template <class... Ms> struct List { using Tab = fuse::Table<Ms...>; using Builder = fuse::TableBuilder<Ms...>; };
   using L = List<

@@ -19,6 +19,10 @@ __global__ __launch_bounds__(512, 4) void body_kernel(const typename Op::Args a)
 EACH(OpF2); EACH(OpF3); EACH(OpF4); EACH(OpF5); EACH(OpRB); EACH(OpOUT); EACH(OpP1); EACH(OpP23); EACH(OpPOUT); EACH(OpINP);
 EACH(OpUP1); EACH(OpRES1A); EACH(OpRES1B); EACH(OpUP2); EACH(T1); EACH(T2); EACH(T3); EACH(GruQ); EACH(GruP); EACH(Vq);
 INST(2, GruQ1); INST(2, GruP1); INST(4, GruQ1); INST(4, GruP1); INST(4, GruQm); INST(4, GruPm);   // the linked cells: last hop; middle hops
+// the rows cell of the tick tables at the phone GRU's size in every link form (the hop-0 phone cell of the four-hop table is the column-split cell: tick.hip.h),
+// and its other split, 16 streams x 128 hidden units
+template __global__ void body_kernel<rc::GruRowsOp<256, 256, 1>, 0>(const GruArgs);
+template __global__ void body_kernel<rc::GruRowsOp<256, 256, 0, 1>, 0>(const GruArgs); template __global__ void body_kernel<rc::GruRowsOp<128, 128, 0, 1>, 0>(const GruArgs);
 // the sparse table's bodies (one hop per step only: tick::sparse_table_at)
 INST(1, OpF4s); INST(1, OpF5s); INST(1, OpRBs); INST(1, OpP1s); INST(1, OpUP1s); INST(1, T1s); INST(1, T2s);
 template __global__ void body_kernel<F1Op2, 0>(const F1Op2::Args);
