@@ -8,21 +8,63 @@
 // bit numbers), for per-body instruction counters (tools/debug/tick_inst_by_body.py); BeatriceBatchMeas_TickOnlyTypes below
 static unsigned long long g_tick_only_types = ~0ull;
 #endif
+// One table under construction.  A body is added by naming its type: the kernel body, the profile name, the argument bank and the
+// placement on the halves of the chip come from tick.hip.h's lists (kBodies, Ops<H>::L)
+template <class Op, class A> static inline auto tick_body_info(const char* name, const A& a, int) -> decltype(Op::info(name, a)) { return Op::info(name, a); }
+template <class Op, class A> static inline auto tick_body_info(const char*, const A& a, long) -> decltype(Op::info(a)) { return Op::info(a); }   // (the op names itself)
+template <int H>
+struct TickTable {
+  using O = tick::Ops<H>;
+  std::unique_ptr<typename O::Builder> tb = std::make_unique<typename O::Builder>();
+  bool sparse = false;
+  int drop = 0;   // measurement builds: BEATRICE_HIP_TICK_DROP
+  bool keep(int group) const { return ((drop >> group) & 1) == 0; }
+  // ... with work figures and a grid stated at the site (the bodies whose ops have no info() / grid())
+  template <tick::BodyType T, class Args>
+  void add_as(const bhip::LaunchInfo& info, const Args& a, dim3 grid, int stage, bool on, double wg_cost) {
+    constexpr tick::Placement place = tick::kBodies[T].place;
+    tb->template add<T>(info, a, grid, stage, on, wg_cost, place != tick::kDealt, place == tick::kPinnedPhoneGru ? 0 : (place == tick::kPinnedPitchGru ? 1 : -1));
+  }
+  // (a type with a sparse form -- one row tile per workgroup, tick.hip.h -- goes into the sparse table in that form)
+  template <tick::BodyType T, class Args>
+  void add_body(const Args& a, int stage, int drop_group, double wg_cost) {
+    using Op = typename O::template Op<T>;
+    if (sparse && tick::kBodies[T].sparse != T) return add_body<tick::kBodies[T].sparse>(a, stage, drop_group, wg_cost);
+    add_as<T>(tick_body_info<Op>(tick::kBodies[T].name, a, 0), a, Op::grid(a), stage, keep(drop_group), wg_cost);
+  }
+};
+// A GRU cell of the tick: one description for every hop of a step and every H.  T0 / TM / TL: the types of hop 0, of the hops between
+// and of the last hop (tick.hip.h GruQ / GruQm / GruQ1); link: [H - 1][B][width] granules between the hops
+template <tick::BodyType T0, tick::BodyType TM, tick::BodyType TL>
+struct TickGruCell {
+  Ring x, h;
+  const float *wih, *whh, *bih, *bhh;
+  unsigned long long* link;
+  int width, stage;
+  double cost0, cost;   // time of a workgroup of hop 0 / of the later hops (us): what two_halves balances on
+  int* link_dead;
+  int passes;
+  template <int H>
+  void add(TickTable<H>& tt, int B, int t) const {
+    auto at = [&](int u) { return link + (size_t)u * B * width; };
+    const GruArgs g{x, h, wih, whh, bih, bhh, nullptr, B, t, t + 1 < H ? at(t) : nullptr, t > 0 ? at(t - 1) : nullptr, H > 1 ? link_dead : nullptr, passes};
+    if (t == 0) tt.template add_body<T0>(g, stage, 1, cost0);
+    else if constexpr (H > 1) {
+      if (t == H - 1) tt.template add_body<TL>(g, stage, 1, cost);
+      else if constexpr (H > 2) tt.template add_body<TM>(g, stage, 1, cost);
+    }
+  }
+};
 template <int H>
 bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   using namespace tick;
   using O = Ops<H>;
   using Tab = typename O::Tab;
-  using OpF2 = typename O::OpF2; using OpF3 = typename O::OpF3; using OpF4 = typename O::OpF4; using OpF5 = typename O::OpF5; using OpRB = typename O::OpRB;
-  using OpOUT = typename O::OpOUT; using OpP1 = typename O::OpP1; using OpP23 = typename O::OpP23; using OpPOUT = typename O::OpPOUT; using OpINP = typename O::OpINP;
-  using OpUP1 = typename O::OpUP1; using OpRES1A = typename O::OpRES1A; using OpRES1B = typename O::OpRES1B; using OpUP2 = typename O::OpUP2;
-  using OpF4s = typename O::OpF4s; using OpF5s = typename O::OpF5s; using OpRBs = typename O::OpRBs; using OpP1s = typename O::OpP1s; using OpUP1s = typename O::OpUP1s;
-  using T1 = typename O::T1; using T2 = typename O::T2; using T3 = typename O::T3; using T1s = typename O::T1s; using T2s = typename O::T2s;
-  using GruQ = typename O::GruQ; using GruP = typename O::GruP; using GruQ1 = typename O::GruQ1; using GruP1 = typename O::GruP1;
-  using GruQm = typename O::GruQm; using GruPm = typename O::GruPm;
   State& k = b->tk;
   if (sparse && !sparse_table_at(H)) { k.table_sparse_total = 0; return true; }   // (no tick of this H runs it: tick_run; its types are fuse::Absent)
-  auto tb = std::make_unique<typename O::Builder>();
+  TickTable<H> tt;
+  tt.sparse = sparse;
+  const auto& tb = tt.tb;
   const PhoneWeights& pw = b->phone_m->w;
   const PitchWeights& qw = b->pitch_m->w;
   const WaveWeights& ww = b->wave_m->w;
@@ -33,19 +75,14 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   const Plan pl = k.plan;
   // measurement aid, MEASUREMENT BUILDS ONLY (tools/debug/build_variant.sh <name> -DBEATRICE_HIP_MEASUREMENT_BUILD; the
   // product library has no switch that changes results): BEATRICE_HIP_TICK_DROP=<bit mask> leaves groups of bodies out of
-  // the launch
+  // the launch (the group numbers at the add_body calls)
 #ifdef BEATRICE_HIP_MEASUREMENT_BUILD
   static const int drop = bhip::meas_env("BEATRICE_HIP_TICK_DROP") ? std::atoi(bhip::meas_env("BEATRICE_HIP_TICK_DROP")) : 0;
-#else
-  constexpr int drop = 0;
-#endif
-  auto keep = [](int group) { return ((drop >> group) & 1) == 0; };
-#ifdef BEATRICE_HIP_MEASUREMENT_BUILD
+  tt.drop = drop;
   tb->only = g_tick_only_types;
 #endif
   // (every body takes its step counter from the launch's StepPairs -- a null counter pointer says so, ring.h stepc)
-  auto hp = [&](int) -> const int* { return nullptr; };
-  auto conv = [&](const Ring& in, const Ring& out, const float* w, const float* bias, int stage) { return conv_args(in, out, w, bias, hp(stage), B); };
+  auto conv = [&](const Ring& in, const Ring& out, const float* w, const float* bias) { return conv_args(in, out, w, bias, nullptr, B); };
   // (workgroups are dispatched in this order: the longest-running bodies first)
   // The GRU cells of a step's hops, linked inside the launch (tick.hip.h): hop 0 publishes into link 0, hop t polls link t - 1 and
   // publishes into link t, the last hop only polls.  A cell must find its predecessor's states published when it starts (it holds a
@@ -60,29 +97,18 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   constexpr double kGruRowsCostP = 25, kGruRowsCostQ = H == 2 ? 14 : 17;
   static const int gru_passes_env = bhip::meas_env("BEATRICE_HIP_GRU_PASSES") ? std::atoi(bhip::meas_env("BEATRICE_HIP_GRU_PASSES")) : 0;
   const int gru_passes = gru_passes_env > 0 ? gru_passes_env : (B >= 512 ? 2 : 1);
-  auto link_p = [&](int t) { return k.d_link_p + (size_t)t * B * 256; };
-  auto link_q = [&](int t) { return k.d_link_q + (size_t)t * B * 128; };
-  auto add_pgru = [&](int t) {
-    if constexpr (H > 1) {
-      GruArgs g{ps.rb[3], ps.h, pw.gru_wih, pw.gru_whh, pw.gru_bih, pw.gru_bhh, hp(Plan::PGRU), B, t, t + 1 < H ? link_p(t) : nullptr, t > 0 ? link_p(t - 1) : nullptr, k.h_link_dead, gru_passes};
-      if (t == 0) tb->template add<T_PGRU>(GruP::info("phone.gru", g), g, GruP::grid(g), Plan::PGRU, keep(1), H == 2 ? kGruRowsCostP : 19);
-      else if (t == H - 1) tb->template add<T_PGRU1>(GruP1::info("phone.gru", g), g, GruP1::grid(g), Plan::PGRU, keep(1), kGruRowsCostP);
-      else if constexpr (H > 2) tb->template add<T_PGRUM>(GruPm::info("phone.gru", g), g, GruPm::grid(g), Plan::PGRU, keep(1), kGruRowsCostP);
-    }
-  };
-  auto add_qgru = [&](int t) {
-    if constexpr (H > 1) {
-      GruArgs g{qs.p[2], qs.h, qw.gru_wih, qw.gru_whh, qw.gru_bih, qw.gru_bhh, hp(Plan::QGRU), B, t, t + 1 < H ? link_q(t) : nullptr, t > 0 ? link_q(t - 1) : nullptr, k.h_link_dead, gru_passes};
-      if (t == 0) tb->template add<T_QGRU>(GruQ::info("pitch.gru", g), g, GruQ::grid(g), Plan::QGRU, keep(1), kGruRowsCostQ);
-      else if (t == H - 1) tb->template add<T_QGRU1>(GruQ1::info("pitch.gru", g), g, GruQ1::grid(g), Plan::QGRU, keep(1), kGruRowsCostQ);
-      else if constexpr (H > 2) tb->template add<T_QGRUM>(GruQm::info("pitch.gru", g), g, GruQm::grid(g), Plan::QGRU, keep(1), kGruRowsCostQ);
-    }
-  };
+  // (hop 0: the column-split cells at one hop per step, 19 / 12 us; the phone cell of hop 0 at four hops is that cell too, tick.hip.h GruP)
+  const TickGruCell<T_PGRU, T_PGRUM, T_PGRU1> pgru{ps.rb[3], ps.h, pw.gru_wih, pw.gru_whh, pw.gru_bih, pw.gru_bhh, k.d_link_p, 256, Plan::PGRU,
+                                                  H == 2 ? kGruRowsCostP : 19, kGruRowsCostP, k.h_link_dead, gru_passes};
+  const TickGruCell<T_QGRU, T_QGRUM, T_QGRU1> qgru{qs.p[2], qs.h, qw.gru_wih, qw.gru_whh, qw.gru_bih, qw.gru_bhh, k.d_link_q, 128, Plan::QGRU,
+                                                  H == 1 ? 12 : kGruRowsCostQ, kGruRowsCostQ, k.h_link_dead, gru_passes};
+  auto add_pgru = [&](int t) { pgru.add(tt, B, t); };
+  auto add_qgru = [&](int t) { qgru.add(tt, B, t); };
   // gru_at(point): the hops placed at insertion point 0 (behind the conditioned blocks), 1 (behind the tail), 2 / 3 (where the second
-  // hop of a two-hop step has always been: behind phone.f2 / wave.inp).  H = 2: hop 1 at 2 (phone) and 3 (pitch); H = 4: hops 1, 2 at
-  // 0, 1 and hop 3 at 2 / 3
+  // hop of a two-hop step has always been: behind phone.f2 / wave.inp).  H = 1: the only hop at 2 (phone) and 3 (pitch), at the END of the
+  // dispatch order; H = 2: hop 1 at 2 and 3; H = 4: hops 1, 2 at 0, 1 and hop 3 at 2 / 3
   auto gru_at = [&](int point) {
-    if constexpr (H == 2) { if (point == 2) add_pgru(1); if (point == 3) add_qgru(1); }
+    if constexpr (H <= 2) { if (point == 2) add_pgru(H - 1); if (point == 3) add_qgru(H - 1); }
     if constexpr (H == 4) {
       if (point == 0) { add_pgru(1); add_qgru(1); }
       if (point == 1) { add_pgru(2); add_qgru(2); }
@@ -90,54 +116,42 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
       if (point == 3) add_qgru(3);
     }
   };
-  add_pgru(0); add_qgru(0);
+  if constexpr (H > 1) { add_pgru(0); add_qgru(0); }
   // ---- longest workgroups first (measured, two per CU): f5 48 us, p1 46, f4 45, rb 42, block halves 41 / 38, tail 36
-  if (!sparse) {
-    { const ConvArgs a = conv(ps.f[3], ps.f[4], pw.f_w[3], pw.f_b[3], Plan::F5); tb->template add<T_F5>(OpF5::info("phone.f5", a), a, OpF5::grid(a), Plan::F5, keep(6), 30); }
-    { const ConvArgs a = conv(qs.spec, qs.p[0], qw.p_w[0], qw.p_b[0], Plan::P1); tb->template add<T_P1>(OpP1::info("pitch.p1", a), a, OpP1::grid(a), Plan::P1, keep(2), 41); }
-    { const ConvArgs a = conv(ps.f[2], ps.f[3], pw.f_w[2], pw.f_b[2], Plan::F4); tb->template add<T_F4>(OpF4::info("phone.f4", a), a, OpF4::grid(a), Plan::F4, keep(6), 28); }
-    for (int i = 0; i < 4; ++i) {
-      const ConvArgs a = conv(i == 0 ? ps.f[4] : ps.rb[i - 1], ps.rb[i], pw.rb_w[i], pw.rb_b[i], Plan::RB0 + i);
-      tb->template add<T_RB>(OpRB::info("phone.rb", a), a, OpRB::grid(a), Plan::RB0 + i, keep(6), 39);
-    }
-  } else {   // (the sparse table: one row tile per workgroup, tick.hip.h)
-    { const ConvArgs a = conv(ps.f[3], ps.f[4], pw.f_w[3], pw.f_b[3], Plan::F5); tb->template add<T_F5S>(OpF5s::info("phone.f5", a), a, OpF5s::grid(a), Plan::F5, keep(6), 30); }
-    { const ConvArgs a = conv(qs.spec, qs.p[0], qw.p_w[0], qw.p_b[0], Plan::P1); tb->template add<T_P1S>(OpP1s::info("pitch.p1", a), a, OpP1s::grid(a), Plan::P1, keep(2), 41); }
-    { const ConvArgs a = conv(ps.f[2], ps.f[3], pw.f_w[2], pw.f_b[2], Plan::F4); tb->template add<T_F4S>(OpF4s::info("phone.f4", a), a, OpF4s::grid(a), Plan::F4, keep(6), 28); }
-    for (int i = 0; i < 4; ++i) {
-      const ConvArgs a = conv(i == 0 ? ps.f[4] : ps.rb[i - 1], ps.rb[i], pw.rb_w[i], pw.rb_b[i], Plan::RB0 + i);
-      tb->template add<T_RBS>(OpRBs::info("phone.rb", a), a, OpRBs::grid(a), Plan::RB0 + i, keep(6), 39);
-    }
-  }
+  // (the sparse table: these in one row tile per workgroup, tick.hip.h)
+  tt.template add_body<T_F5>(conv(ps.f[3], ps.f[4], pw.f_w[3], pw.f_b[3]), Plan::F5, 6, 30);
+  tt.template add_body<T_P1>(conv(qs.spec, qs.p[0], qw.p_w[0], qw.p_b[0]), Plan::P1, 2, 41);
+  tt.template add_body<T_F4>(conv(ps.f[2], ps.f[3], pw.f_w[2], pw.f_b[2]), Plan::F4, 6, 28);
+  for (int i = 0; i < 4; ++i) tt.template add_body<T_RB>(conv(i == 0 ? ps.f[4] : ps.rb[i - 1], ps.rb[i], pw.rb_w[i], pw.rb_b[i]), Plan::RB0 + i, 6, 39);
   // conditioned blocks: two row-local chains each
   for (int blk = 0; blk < B_NBLOCKS; ++blk) {
     const WaveState::Scratch& sc = ws.scr[blk];  // one scratch set per block: all four blocks are in flight at once
     const int s0 = pl.blk(blk);
     const rc::BlockBArgs ba{sc.xa, ws.x[blk + 1], ww.q_w[blk], ww.q_b[blk], ww.o_w[blk], ww.o_b[blk], ws.d_kt[blk], ws.d_v[blk],
-                            b->dev_view<int>(b->off.perm[blk]), b->dev_view<int>(b->off.tile_slot[blk]), hp(s0 + 1)};
-    tb->template add<T_BLKB>(LaunchInfo{"wave.blk.b", 2.0 * B * H * (256.0 * 256 * 2 + 256.0 * 384 * 2), 4.0 * (2.0 * 256 * 256 + 2.0 * 256 * 384 + B * H * 3.0 * 256)}, ba,
-                    dim3(ws.n_tiles_max, 1), s0 + 1, keep(5), 43.0);
+                            b->dev_view<int>(b->off.perm[blk]), b->dev_view<int>(b->off.tile_slot[blk]), nullptr};
+    tt.template add_as<T_BLKB>(LaunchInfo{kBodies[T_BLKB].name, 2.0 * B * H * (256.0 * 256 * 2 + 256.0 * 384 * 2), 4.0 * (2.0 * 256 * 256 + 2.0 * 256 * 384 + B * H * 3.0 * 256)}, ba,
+                               dim3(ws.n_tiles_max, 1), s0 + 1, tt.keep(5), 43.0);
     if (quads_on(b)) {  // rows without 15 neighbours on their K/V slot: one workgroup per quad (rebuild_tiles decides which rows)
       const rc::BlockBqArgs bq{sc.xa, ws.x[blk + 1], ww.q_w[blk], ww.q_b[blk], ww.o_w[blk], ww.o_b[blk], ws.d_ktp[blk], ws.d_vp[blk],
-                               b->dev_view<int>(b->off.qperm[blk]), b->dev_view<int>(b->off.qslot[blk]), hp(s0 + 1)};
+                               b->dev_view<int>(b->off.qperm[blk]), b->dev_view<int>(b->off.qslot[blk]), nullptr};
       // (a slot leaves at most 7 rows = 2 quads to this list: <= n_slots workgroups of two quads)
-      tb->template add<T_BLKBQ>(LaunchInfo{"wave.blk.bq", 0.0, 0.0}, bq, dim3(std::min(2 * ws.n_tiles_max, ws.n_slots), 1), s0 + 1, keep(5), 42.0);
+      tt.template add_as<T_BLKBQ>(LaunchInfo{kBodies[T_BLKBQ].name, 0.0, 0.0}, bq, dim3(std::min(2 * ws.n_tiles_max, ws.n_slots), 1), s0 + 1, tt.keep(5), 42.0);
     }
   }
   for (int blk = 0; blk < B_NBLOCKS; ++blk) {
-    const rc::BlockAArgs aa{ws.x[blk], ws.scr[blk].xa, ww.c1_w[blk], ww.c1_b[blk], ww.c2_w[blk], ww.c2_b[blk], hp(pl.blk(blk)), B};
-    switch (blk) {
-      case 0: tb->template add<T_BLKA1>(rc::BlockAOp<1, H>::info(aa), aa, rc::BlockAOp<1, H>::grid(aa), pl.blk(blk), keep(5), 38); break;
-      case 1: tb->template add<T_BLKA2>(rc::BlockAOp<2, H>::info(aa), aa, rc::BlockAOp<2, H>::grid(aa), pl.blk(blk), keep(5), 38); break;
-      case 2: tb->template add<T_BLKA4>(rc::BlockAOp<4, H>::info(aa), aa, rc::BlockAOp<4, H>::grid(aa), pl.blk(blk), keep(5), 38); break;
-      default: tb->template add<T_BLKA8>(rc::BlockAOp<8, H>::info(aa), aa, rc::BlockAOp<8, H>::grid(aa), pl.blk(blk), keep(5), 38); break;
+    const rc::BlockAArgs aa{ws.x[blk], ws.scr[blk].xa, ww.c1_w[blk], ww.c1_b[blk], ww.c2_w[blk], ww.c2_b[blk], nullptr, B};
+    switch (blk) {   // (the block's dilation is its type)
+      case 0: tt.template add_body<T_BLKA1>(aa, pl.blk(blk), 5, 38); break;
+      case 1: tt.template add_body<T_BLKA2>(aa, pl.blk(blk), 5, 38); break;
+      case 2: tt.template add_body<T_BLKA4>(aa, pl.blk(blk), 5, 38); break;
+      default: tt.template add_body<T_BLKA8>(aa, pl.blk(blk), 5, 38); break;
     }
   }
   gru_at(0);
   // (the k-NN lookup: one workgroup per stream walks the step's hops against the stream's codebook -- 35 us at four hops per step with
   //  64 speakers' codebooks in play.  At the end of the table, where round 2 had put it by its one-hop cost, it ENDED the launch: 256
   //  workgroups alone on the chip from 229 to 283 us of configs[3]'s tick, profiles/r06_notes.md section 3.  Present only while some stream has k > 0)
-  { const VqArgs a{H, ps.raw, phone_vector_ring(ps), hp(Plan::VQ), ps.d_cbT, ps.d_cnorm, ps.d_vqk}; tb->template add<T_VQ>(LaunchInfo{"phone.vq", 0, 4.0 * B * H * 256}, a, dim3(B, 1), Plan::VQ, !ps.skip_vq, 9.0 * H, true); }
+  { const VqArgs a{H, ps.raw, phone_vector_ring(ps), nullptr, ps.d_cbT, ps.d_cnorm, ps.d_vqk}; tt.template add_as<T_VQ>(LaunchInfo{kBodies[T_VQ].name, 0, 4.0 * B * H * 256}, a, dim3(B, 1), Plan::VQ, !ps.skip_vq, 9.0 * H); }
   {
     // the tail as three stages, several streams per workgroup (tail_stages.hip.h); same weights, same state block
     tst::StageArgs t1{}, t2{}, t3{};
@@ -147,104 +161,60 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
     t2.w[0] = ww.ra_w[2]; t2.b[0] = ww.ra_b[2]; t2.w[1] = ww.rb_w[2]; t2.b[1] = ww.rb_b[2]; t2.w[2] = ww.up_w[3]; t2.b[2] = ww.up_b[3];
     t3.w[0] = ww.ra_w[3]; t3.b[0] = ww.ra_b[3]; t3.w[1] = ww.rb_w[3]; t3.b[1] = ww.rb_b[3];
     t3.fin_w = ww.fin_w; t3.fin_b = ww.fin_b; t3.d_out = ws.d_out; t3.io_stride = ws.io_stride;
-    if (!sparse) {
-      tb->template add<T_TAIL1>(T1::info(t1), t1, T1::grid(t1), pl.tail(), keep(4), 28, true);
-      tb->template add<T_TAIL2>(T2::info(t2), t2, T2::grid(t2), pl.tail() + 1, keep(4), 11.5 * H, true);
-    } else {   // (never occupied while the sparse table is in use; kept so that the two tables hold the same stages)
-      tb->template add<T_TAIL1S>(T1s::info(t1), t1, T1s::grid(t1), pl.tail(), keep(4), 28, true);
-      tb->template add<T_TAIL2S>(T2s::info(t2), t2, T2s::grid(t2), pl.tail() + 1, keep(4), 11.5 * H, true);
-    }
-    tb->template add<T_TAIL3>(T3::info(t3), t3, T3::grid(t3), pl.tail() + 2, keep(4), 6.5 * H, true);
+    // (the sparse forms are never occupied while the sparse table is in use; kept so that the two tables hold the same stages)
+    tt.template add_body<T_TAIL1>(t1, pl.tail(), 4, 28);
+    tt.template add_body<T_TAIL2>(t2, pl.tail() + 1, 4, 11.5 * H);
+    tt.template add_body<T_TAIL3>(t3, pl.tail() + 2, 4, 6.5 * H);
   }
   gru_at(1);
   // ---- everything else, longest workgroups first (they start when the heavy ones above leave their slots)
   // (the pitch head: few workgroups that walk a step's hops one after the other -- 10 us per workgroup at two hops per step, 21 at four;
   //  at the end of the table, where its instruction count would put it, it ENDED the launch: round 5's timelines, profiles/r05_notes.md)
-  { PitchHeadArgs a = head_args(qw, qs); a.hop = hp(Plan::HEAD); tb->template add<T_HEAD>(head_info(qs), a, dim3((B + 7) / 8, 1), Plan::HEAD, keep(0), 7.5 * H); }
-  { const ConvArgs a = conv(ps.f[1], ps.f[2], pw.f_w[1], pw.f_b[1], Plan::F3); tb->template add<T_F3>(OpF3::info("phone.f3", a), a, OpF3::grid(a), Plan::F3, keep(6), 15); }
-  if (!sparse) { const ConvArgs a = conv(ws.x[4], ws.ya1, ww.up_w[0], ww.up_b[0], pl.up1()); tb->template add<T_UP1>(OpUP1::info("wave.up1", a), a, OpUP1::grid(a), pl.up1(), keep(7), 14); }
-  else { const ConvArgs a = conv(ws.x[4], ws.ya1, ww.up_w[0], ww.up_b[0], pl.up1()); tb->template add<T_UP1S>(OpUP1s::info("wave.up1", a), a, OpUP1s::grid(a), pl.up1(), keep(7), 14); }
-  { const ConvArgs a = conv(ws.yb1, ws.yc1, ww.rb_w[0], ww.rb_b[0], pl.up1() + 2); tb->template add<T_RES1B>(OpRES1B::info("wave.res1b", a), a, OpRES1B::grid(a), pl.up1() + 2, keep(7), 13); }
-  { const ConvArgs a = conv(ws.ya1, ws.yb1, ww.ra_w[0], ww.ra_b[0], pl.up1() + 1); tb->template add<T_RES1A>(OpRES1A::info("wave.res1a", a), a, OpRES1A::grid(a), pl.up1() + 1, keep(7), 13); }
-  { const ConvArgs a = conv(ws.yc1, ws.ya2, ww.up_w[1], ww.up_b[1], pl.up1() + 3); tb->template add<T_UP2>(OpUP2::info("wave.up2", a), a, OpUP2::grid(a), pl.up1() + 3, keep(7), 13); }
-  { const ConvArgs a = conv(ps.f[0], ps.f[1], pw.f_w[0], pw.f_b[0], Plan::F2); tb->template add<T_F2>(OpF2::info("phone.f2", a), a, OpF2::grid(a), Plan::F2, keep(6), 15); }
-  if constexpr (H == 1) { const GruArgs g{ps.rb[3], ps.h, pw.gru_wih, pw.gru_whh, pw.gru_bih, pw.gru_bhh, hp(Plan::PGRU), B, 0, nullptr, nullptr, nullptr, gru_passes}; tb->template add<T_PGRU>(GruP::info("phone.gru", g), g, GruP::grid(g), Plan::PGRU, keep(1), 19); }
+  { PitchHeadArgs a = head_args(qw, qs); a.hop = nullptr; tt.template add_as<T_HEAD>(head_info(qs), a, dim3((B + 7) / 8, 1), Plan::HEAD, tt.keep(0), 7.5 * H); }
+  tt.template add_body<T_F3>(conv(ps.f[1], ps.f[2], pw.f_w[1], pw.f_b[1]), Plan::F3, 6, 15);
+  tt.template add_body<T_UP1>(conv(ws.x[4], ws.ya1, ww.up_w[0], ww.up_b[0]), pl.up1(), 7, 14);
+  tt.template add_body<T_RES1B>(conv(ws.yb1, ws.yc1, ww.rb_w[0], ww.rb_b[0]), pl.up1() + 2, 7, 13);
+  tt.template add_body<T_RES1A>(conv(ws.ya1, ws.yb1, ww.ra_w[0], ww.ra_b[0]), pl.up1() + 1, 7, 13);
+  tt.template add_body<T_UP2>(conv(ws.yc1, ws.ya2, ww.up_w[1], ww.up_b[1]), pl.up1() + 3, 7, 13);
+  tt.template add_body<T_F2>(conv(ps.f[0], ps.f[1], pw.f_w[0], pw.f_b[0]), Plan::F2, 6, 15);
   gru_at(2);
-  { const ConvArgs a = conv(qs.h, qs.logits, qw.out_w, qw.out_b, Plan::POUT); tb->template add<T_POUT>(OpPOUT::info("pitch.out", a), a, OpPOUT::grid(a), Plan::POUT, keep(2), 11); }
-  for (int i = 0; i < 2; ++i) {
-    const ConvArgs a = conv(qs.p[i], qs.p[i + 1], qw.p_w[i + 1], qw.p_b[i + 1], Plan::P2 + i);
-    tb->template add<T_P23>(OpP23::info("pitch.p23", a), a, OpP23::grid(a), Plan::P2 + i, keep(2), 10);
-  }
-  { const Ring phone_in{ws.d_phone, B_PHONE_CH, H, ws.front_slots}; ConvArgs a = conv(phone_in, ws.x[0], ww.inp_w, ww.inp_b, Plan::INP); a.res = ws.e; tb->template add<T_INP>(OpINP::info("wave.inp", a), a, OpINP::grid(a), Plan::INP, keep(3), 7.5); }
-  if constexpr (H == 1) { const GruArgs g{qs.p[2], qs.h, qw.gru_wih, qw.gru_whh, qw.gru_bih, qw.gru_bhh, hp(Plan::QGRU), B, 0, nullptr, nullptr, nullptr, gru_passes}; tb->template add<T_QGRU>(GruQ::info("pitch.gru", g), g, GruQ::grid(g), Plan::QGRU, keep(1), 12); }
+  tt.template add_body<T_POUT>(conv(qs.h, qs.logits, qw.out_w, qw.out_b), Plan::POUT, 2, 11);
+  for (int i = 0; i < 2; ++i) tt.template add_body<T_P23>(conv(qs.p[i], qs.p[i + 1], qw.p_w[i + 1], qw.p_b[i + 1]), Plan::P2 + i, 2, 10);
+  { const Ring phone_in{ws.d_phone, B_PHONE_CH, H, ws.front_slots}; ConvArgs a = conv(phone_in, ws.x[0], ww.inp_w, ww.inp_b); a.res = ws.e; tt.template add_body<T_INP>(a, Plan::INP, 3, 7.5); }
   gru_at(3);
-  { FftArgs a = fft_args(qw, qs); a.hop = hp(Plan::FFT); tb->template add<T_FFT>(fft_info(qs), FftArgs2{a, B}, dim3((B + 1) / 2, H), Plan::FFT, keep(0), 8.7); }
-  { const ConvArgs a = conv(ps.h, phone_out_ring(ps), pw.out_w, pw.out_b, Plan::OUT); tb->template add<T_OUT>(OpOUT::info("phone.out", a), a, OpOUT::grid(a), Plan::OUT, keep(3), 4.5); }
-  { F1Args a = f1_args(pw, ps); a.hop = hp(Plan::F1); a.hop_publish = nullptr; a.hop_publish_wave = nullptr; tb->template add<T_F1>(f1_info(ps), F1Args2{a, B}, dim3((B + 1) / 2, H), Plan::F1, keep(0), 3.7); }
-  { CondArgs a = cond_args(ww, ws); a.hop = hp(Plan::COND); a.hop_next_out = nullptr; tb->template add<T_COND>(cond_info(ws), a, dim3((B * H + 1) / 2, 1), Plan::COND, keep(0), 1.5); }
+  { FftArgs a = fft_args(qw, qs); a.hop = nullptr; tt.template add_as<T_FFT>(fft_info(qs), FftArgs2{a, B}, dim3((B + 1) / 2, H), Plan::FFT, tt.keep(0), 8.7); }
+  tt.template add_body<T_OUT>(conv(ps.h, phone_out_ring(ps), pw.out_w, pw.out_b), Plan::OUT, 3, 4.5);
+  { F1Args a = f1_args(pw, ps); a.hop = nullptr; a.hop_publish = nullptr; a.hop_publish_wave = nullptr; tt.template add_as<T_F1>(f1_info(ps), F1Args2{a, B}, dim3((B + 1) / 2, H), Plan::F1, tt.keep(0), 3.7); }
+  { CondArgs a = cond_args(ww, ws); a.hop = nullptr; a.hop_next_out = nullptr; tt.template add_as<T_COND>(cond_info(ws), a, dim3((B * H + 1) / 2, 1), Plan::COND, tt.keep(0), 1.5); }
   if (!tb->ok) return false;
   // (XCD-aware placement -- bodies with many weights pinned to one XCD, or to the XCDs of equal index modulo 2 / 4, so that their weights
   //  stay in fewer L2s -- was measured in rounds 2 and 4: memory-side traffic / 4, the launch 4-8 % slower; the switch went with the
-  //  span lookup in round 5.  Its successor is TableBuilder::two_halves below: the same idea at the granularity that costs nothing)
+  //  span lookup in round 5.  Its successor is fuse::two_halves (tick_order_plan.h): the same idea at the granularity that costs nothing;
+  //  which bodies it pins -- the ones with the weights, each on one half of the chip -- is tick::kBodies' placement column)
   // Dispatch order by workgroup (fuse::WgDesc, one descriptor per workgroup read by a scalar load): the bodies in the order added above,
   // every body a contiguous run.  (Round 5 also measured the short workgroups dealt AMONG the long MFMA-dense ones: 7.7 % slower,
   // profiles/r05_notes.md section 4; round 6 the short ones as a KERNEL OF THEIR OWN at twice the occupancy, beside or behind the dense
   // one: 8-12 % slower, profiles/r06_notes.md section 1, tools/experiments/r06_two_kernel_tick.patch.)
   static const int halves_mode = bhip::meas_env("BEATRICE_HIP_TICK_HALVES") ? std::atoi(bhip::meas_env("BEATRICE_HIP_TICK_HALVES")) : 2;   // 0: every body on all XCDs; 2 (default): halves; 4: quarters
   {
-    std::vector<fuse::WgDesc> desc;
-    bool pinned[fuse::kMaxSpans];
-    int group[fuse::kMaxSpans];
-    for (int i = 0; i < tb->t.n_spans; ++i) {   // the bodies with the weights, each on one half of the chip (TableBuilder::two_halves)
-      group[i] = -1;
-      switch (tb->t.span[i].type) {
-        case T_PGRU: case T_PGRU1: case T_PGRUM: pinned[i] = true; group[i] = 0; break;
-        case T_QGRU: case T_QGRU1: case T_QGRUM: pinned[i] = true; group[i] = 1; break;
-        case T_F2: case T_F3: case T_F4: case T_F5: case T_P1: case T_RB: case T_F4S: case T_F5S: case T_P1S: case T_RBS:
-        case T_BLKA1: case T_BLKA2: case T_BLKA4: case T_BLKA8: case T_BLKB: case T_BLKBQ:
-        case T_UP1: case T_UP1S: case T_RES1A: case T_RES1B: case T_UP2: case T_POUT: case T_P23: case T_INP: case T_OUT: pinned[i] = true; break;
-        default: pinned[i] = false; break;   // (the tail stages and the per-stream bodies: hardly any weights)
-      }
-    }
-    if (halves_mode != 0 && !sparse) {   // (the sparse table only ever runs partly filled ticks)
-      desc = tb->two_halves(pinned, group, halves_mode == 4 ? 4 : 2);
-    } else {
-      desc = tb->in_span_order();
-    }
+    const fuse::SpanRow* rows = tb->rows;
+    const int n_rows = tb->t.n_spans;
+    const std::vector<fuse::WgDesc> plain = fuse::in_span_order(rows, n_rows);
+    // (the sparse table only ever runs partly filled ticks)
+    const std::vector<fuse::WgDesc> desc = halves_mode != 0 && !sparse ? fuse::two_halves(rows, n_rows, halves_mode == 4 ? 4 : 2) : plain;
     auto upload = [&](const std::vector<fuse::WgDesc>& v, DevBuf<fuse::WgDesc>& d_desc) {
       if (v.size() > d_desc.size() && !d_desc.alloc(v.size(), "tick dispatch order", false)) return false;
       if (!v.empty()) BHIP_TRY(hipMemcpy(d_desc, v.data(), sizeof(fuse::WgDesc) * v.size(), hipMemcpyHostToDevice));
       return true;
     };
     if (!sparse) {   // (the order of partly filled ticks: tick_launch)
-      const std::vector<fuse::WgDesc> plain = tb->in_span_order();
       if (!upload(plain, k.d_desc_plain)) return false;
       k.table_total_plain = (int)plain.size();
       // the fill / drain shapes without the empty stages' workgroups (tick::State::d_desc_ranges)
-      for (auto& row : k.range_n) for (int& n : row) n = 0;
-      const int n_stages = pl.count();
-      // ... and, from kRangeHalvesFrom occupied stages on, in the halves order worked out for exactly the stages they hold (round 6: a
-      // nearly full tick gains from the halves what a full one does; profiles/r06_notes.md section 9)
       static const int range_halves_from = bhip::meas_env("BEATRICE_HIP_TICK_RANGE_HALVES") ? std::atoi(bhip::meas_env("BEATRICE_HIP_TICK_RANGE_HALVES")) : kRangeHalvesFrom;
-      if (plain.size() <= 16384 && n_stages <= kMaxStages) {
-        std::vector<fuse::WgDesc> all;
-        for (int shape = 0; shape < 2; ++shape)
-          for (int s0 = 0; s0 < n_stages; ++s0) {
-            k.range_off[shape][s0] = all.size();
-            const int occupied = shape == 0 ? s0 + 1 : n_stages - s0;
-            if (halves_mode != 0 && occupied >= range_halves_from) {
-              const std::vector<fuse::WgDesc> part = shape == 0 ? tb->two_halves(pinned, group, 2, 0, s0) : tb->two_halves(pinned, group, 2, s0, 255);
-              all.insert(all.end(), part.begin(), part.end());
-            } else {
-              for (const fuse::WgDesc& d : plain) {
-                const int stage = (d.arg >> 16) & 0xff;
-                if (shape == 0 ? stage <= s0 : stage >= s0) all.push_back(d);
-              }
-            }
-            k.range_n[shape][s0] = (int)(all.size() - k.range_off[shape][s0]);
-          }
-        if (!upload(all, k.d_desc_ranges)) return false;
-      }
+      const fuse::RangeLists r = fuse::range_lists(rows, n_rows, plain, pl.count(), halves_mode, range_halves_from);
+      k.range = r.at;
+      if (!r.all.empty() && !upload(r.all, k.d_desc_ranges)) return false;
     }
     tb->t.total = (int)desc.size();   // (two_halves may add filler indices)
     if (!upload(desc, sparse ? k.d_desc_sparse : k.d_desc)) return false;
@@ -295,14 +265,8 @@ static void tick_launch(BeatriceBatch* b, const bool sparse, const bool full, hi
   int total = sparse ? k.table_sparse_total : (full ? k.table_total : k.table_total_plain);
   static const bool no_ranges = bhip::meas_env("BEATRICE_HIP_TICK_NO_RANGES") != nullptr;   // A/B switch for measurements
   if (!sparse && !full && !no_ranges && k.d_desc_ranges.get() != nullptr) {
-    const int n_stages = k.plan.count();
-    int lo = n_stages, hi = -1, occupied = 0;
-    for (int s = 0; s < n_stages; ++s) if (pairs.hop[s] >= 0) { lo = s < lo ? s : lo; hi = s; ++occupied; }
-    if (occupied > 0 && occupied == hi - lo + 1) {
-      const int shape = lo == 0 ? 0 : (hi == n_stages - 1 ? 1 : -1);
-      const int at = shape == 0 ? hi : lo;
-      if (shape >= 0 && k.range_n[shape][at] > 0) { desc = k.d_desc_ranges + k.range_off[shape][at]; total = k.range_n[shape][at]; }
-    }
+    const fuse::RangePick pick = fuse::pick_range(pairs.hop, k.plan.count(), k.range);
+    if (pick.shape >= 0) { desc = k.d_desc_ranges + k.range.off[pick.shape][pick.at]; total = k.range.n[pick.shape][pick.at]; }
   }
   if (total <= 0) return;
   // (k.ragged: the second instance of the launch, once a stream has sat a step out -- at several hops per step a stream sits a WHOLE step out)

@@ -23,6 +23,7 @@
 
 #include "engine.h"
 #include "ring.h"
+#include "tick_order_plan.h"
 
 namespace fuse {
 
@@ -123,13 +124,10 @@ struct Absent : Op {
   __device__ static __forceinline__ void run(const Args&, int, int, float*) {}
   template <bool RAG> __device__ static __forceinline__ void run_t(const Args&, int, int, float*) {}
 };
-struct Span { int first, gx, type, arg; };  // workgroups [first, next first) run body `type` with its argument block `arg`
-constexpr int kMaxSpans = 64;
-// (bits 16-23 of Span::arg: the body's pipeline stage, see StepPairs)
+// (Span, WgDesc, kMaxSpans, kMaxStepPairs: tick_order_plan.h -- the host-side order of a launch is worked out there, without HIP)
 // Step counter and I/O slot of every pipeline stage for ONE launch, passed to the table kernel by value (kernel arguments):
 // a workgroup looks its body's stage up and leaves the pair in LDS for the body (stepc, ring.h); a stage whose counter is
 // negative has no step in this launch and its workgroups leave at once.
-constexpr int kMaxStepPairs = 32;
 // hv / hopv / n_streams: ragged steps (ring.h stepc::hopv) -- stage s reads its per-stream counters at hopv + hv[s] * n_streams
 // (hv[s] < 0 or hopv null: every stream is at hop[s])
 struct StepPairs { int hop[kMaxStepPairs], io[kMaxStepPairs], hv[kMaxStepPairs]; const int* hopv; int n_streams; };
@@ -140,10 +138,6 @@ struct Banks<M, Rest...> {
   typename M::op::Args a[M::cap];
   Banks<Rest...> rest;
 };
-// One workgroup of a launch whose dispatch ORDER is free (Table::desc): body type, argument block | stage << 16 (as Span::arg),
-// the workgroup's index inside its body, the body's grid x-extent.  With a descriptor per workgroup the order is free:
-// TableBuilder::two_halves() puts every body with weights on one half of the chip.
-struct WgDesc { int type, arg, local, gx; };
 template <class... Ms>
 struct Table {
   int n_spans, total, unused0, unused1;
@@ -239,75 +233,22 @@ template <class... Ms>
 struct TableBuilder {
   Table<Ms...> t{};
   int used[sizeof...(Ms)] = {};
-  double cost[kMaxSpans] = {};  // estimated time of the body's workgroups (us, from the launch's timelines): what two_halves balances
-  int n_wg[kMaxSpans] = {};
+  SpanRow rows[kMaxSpans] = {};   // the bodies as the dispatch order sees them (tick_order_plan.h); rows[i] goes with t.span[i]
   TableBuilder() { for (Span& sp : t.span) sp = Span{0x7fffffff, 1, -1, 0}; }
   bool ok = true;
   double flops = 0, bytes = 0;
   unsigned long long only = ~0ull;   // measurement builds (batch_tick.hip.h): bit I clear = bodies of type I are left out of the table
-  // the workgroups in the order the bodies were added (every body a contiguous run)
-  std::vector<WgDesc> in_span_order() const {
-    std::vector<WgDesc> out;
-    for (int i = 0; i < t.n_spans; ++i)
-      for (int w = 0; w < n_wg[i]; ++w) out.push_back(WgDesc{t.span[i].type, t.span[i].arg, w, t.span[i].gx});
-    return out;
-  }
-  // Two HALVES of the chip.  Workgroup i of a launch runs on XCD i % 8 (observed; used for speed only), so the indices with
-  // i % 8 < 4 and those with i % 8 >= 4 are two queues, four XCDs each.  A body flagged `pinned` goes whole into ONE queue (the
-  // one with less estimated time so far, cost[]; spans that name the same `group` >= 0 share a queue: the linked GRU cells of a
-  // step's hops), so its weights pass through four of the eight L2s instead of all of them; the other bodies are dealt to both
-  // queues, more to the one that is behind.  Order inside a queue = the order added.  The launch's memory-side traffic falls by
-  // half the pinned bodies' weights x 8 (profiles/r05_notes.md); what it may cost is balance: the two halves no longer share one
-  // queue of work.
-  // stage_lo .. stage_hi: only the bodies of these stages (a partly filled tick's list, balanced over the halves for what it holds)
-  std::vector<WgDesc> two_halves(const bool* pinned, const int* group, const int NQ = 2 /* queues: 2 halves or 4 quarters of the chip */,
-                                 const int stage_lo = 0, const int stage_hi = 255) const {
-    struct Item { int span, local; };
-    std::vector<Item> q[4];
-    double load[4] = {0, 0, 0, 0};
-    int group_q[kMaxSpans];
-    for (int& g : group_q) g = -1;
-    auto lightest = [&]() { int h = 0; for (int x = 1; x < NQ; ++x) if (load[x] < load[h]) h = x; return h; };
-    for (int i = 0; i < t.n_spans; ++i) {
-      const int stage = (t.span[i].arg >> 16) & 0xff;
-      if (stage < stage_lo || stage > stage_hi) continue;
-      const double c = n_wg[i] > 0 ? cost[i] / n_wg[i] : 0.0;
-      if (pinned[i]) {
-        int h = lightest();
-        if (group[i] >= 0 && group[i] < kMaxSpans) { if (group_q[group[i]] >= 0) h = group_q[group[i]]; else group_q[group[i]] = h; }
-        for (int w = 0; w < n_wg[i]; ++w) q[h].push_back(Item{i, w});
-        load[h] += cost[i];
-      } else {
-        for (int w = 0; w < n_wg[i]; ++w) { const int h = lightest(); q[h].push_back(Item{i, w}); load[h] += c; }
-      }
-    }
-    std::vector<WgDesc> out;
-    auto emit = [&](const Item& x) { const Span& sp = t.span[x.span]; out.push_back(WgDesc{sp.type, sp.arg, x.local, sp.gx}); };
-    size_t at[4] = {0, 0, 0, 0};
-    auto all_have = [&]() { for (int h = 0; h < NQ; ++h) if (at[h] >= q[h].size()) return false; return true; };
-    while (all_have()) {   // 8 / NQ consecutive indices (= XCDs) for each queue in turn
-      for (int h = 0; h < NQ; ++h)
-        for (int j = 0; j < 8 / NQ; ++j) {
-          if (at[h] < q[h].size()) emit(q[h][at[h]++]);
-          else out.push_back(WgDesc{-1, 0, 0, 1});   // (a filler index: that slot's turn passes)
-        }
-    }
-    for (bool more = true; more;) {   // (the longer queues' rests go to all eight XCDs, round-robin)
-      more = false;
-      for (int h = 0; h < NQ; ++h) if (at[h] < q[h].size()) { emit(q[h][at[h]++]); more = true; }
-    }
-    return out;
-  }
+  // wg_cost: estimated time of one of the body's workgroups; pinned / group: its placement on the halves of the chip (two_halves)
   template <int I, class Args>
-  void add(const bhip::LaunchInfo& info, const Args& a, dim3 grid, int stage, bool on = true, double wg_cost = 1.0, bool spread_over_xcds = false) {
+  void add(const bhip::LaunchInfo& info, const Args& a, dim3 grid, int stage, bool on, double wg_cost, bool pinned, int group) {
     if (!on || ((only >> I) & 1) == 0) return;
     using BA = BankAt<I, Banks<Ms...>>;
     if (t.n_spans >= kMaxSpans || used[I] >= BA::cap) { ok = false; return; }
     BA::get(t.banks)[used[I]] = a;
     Span& sp = t.span[t.n_spans];
     sp.first = t.total; sp.gx = (int)grid.x > 0 ? (int)grid.x : 1; sp.type = I; sp.arg = used[I]++ | (stage << 16);
-    n_wg[t.n_spans] = (int)(grid.x * grid.y);
-    cost[t.n_spans] = wg_cost * n_wg[t.n_spans];
+    const int n_wg = (int)(grid.x * grid.y);
+    rows[t.n_spans] = SpanRow{sp.type, sp.arg, sp.gx, n_wg, wg_cost * n_wg, pinned, group};
     ++t.n_spans;
     t.total += (int)(grid.x * grid.y);
     flops += info.flops; bytes += info.bytes;

@@ -23,7 +23,9 @@
 //     byte range a consumer stage reads from its step's snapshot into that stage's private arrays at the tick the step
 //     arrives there (consumers: k-NN, pitch head, conditioning mix, the attention half of each block).
 #pragma once
+#include <tuple>
 #include <type_traits>
+#include <utility>
 
 #include "chain_layers.hip.h"
 #include "fuse.hip.h"
@@ -35,7 +37,7 @@
 namespace tick {
 
 constexpr int kRangeHalvesFrom = 99;   // a partly filled tick with at least this many occupied stages runs in its own halves order (99: none does)
-constexpr int kMaxStages = 32, kRing = 64, kMaxCopies = 16;  // (copies: 7 consumers + the snapshot upload)
+constexpr int kMaxStages = fuse::kMaxStepPairs, kRing = 64, kMaxCopies = 16;  // (copies: 7 consumers + the snapshot upload)
 
 struct Copy { unsigned char* dst; const unsigned char* src; int bytes; };
 constexpr int kCopyChunk = 4096;  // bytes one workgroup moves (256 lanes x 16 bytes, one round trip)
@@ -83,6 +85,44 @@ enum BodyType {
   T_QGRU, T_PGRU, T_VQ, T_TAIL1, T_TAIL2, T_TAIL3, T_BLKA1, T_BLKA2, T_BLKA4, T_BLKA8, T_BLKB, T_BLKBQ,
   T_F4S, T_F5S, T_RBS, T_P1S, T_UP1S, T_TAIL1S, T_TAIL2S, T_QGRU1, T_PGRU1, T_QGRUM, T_PGRUM, T_COUNT
 };
+// What the host knows of a body type whatever the hops per step: the ONE list a new type is entered in (the enum above gives it its
+// number, Ops<H>::L below its kernel body; both are checked against this list when they are compiled).
+// Placement on the halves of the chip (fuse::two_halves): the bodies with the weights go whole to one half; the GRU cells of a step's
+// hops, linked inside the launch, share one.  A type states its class: there is no default.
+enum Placement { kDealt /* hardly any weights: dealt to both halves */, kPinned, kPinnedPhoneGru /* group 0 */, kPinnedPitchGru /* group 1 */ };
+struct Body {
+  BodyType type;
+  const char* name;   // profile name
+  int cap;            // bodies of the type a table may hold (its argument bank)
+  Placement place;
+  BodyType sparse;    // the type's form in the sparse table (itself: the same body in both -- the default)
+  bool spread;        // per-stream bodies asked for on all eight XCDs (what kDealt does: checked below)
+  constexpr Body(BodyType t, const char* n, int c, Placement p, BodyType s = T_COUNT, bool sp = false) : type(t), name(n), cap(c), place(p), sparse(s == T_COUNT ? t : s), spread(sp) {}
+};
+constexpr Body kBodies[] = {
+    {T_F1, "phone.f1", 1, kDealt}, {T_FFT, "pitch.fft", 1, kDealt}, {T_F2, "phone.f2", 1, kPinned}, {T_F3, "phone.f3", 1, kPinned},
+    {T_F4, "phone.f4", 1, kPinned, T_F4S}, {T_F5, "phone.f5", 1, kPinned, T_F5S}, {T_P1, "pitch.p1", 1, kPinned, T_P1S}, {T_RB, "phone.rb", 4, kPinned, T_RBS},
+    {T_P23, "pitch.p23", 2, kPinned}, {T_POUT, "pitch.out", 1, kPinned}, {T_HEAD, "pitch.head", 1, kDealt}, {T_OUT, "phone.out", 1, kPinned},
+    {T_COND, "wave.cond", 1, kDealt}, {T_INP, "wave.inp", 1, kPinned}, {T_UP1, "wave.up1", 1, kPinned, T_UP1S}, {T_RES1A, "wave.res1a", 1, kPinned},
+    {T_RES1B, "wave.res1b", 1, kPinned}, {T_UP2, "wave.up2", 1, kPinned}, {T_QGRU, "pitch.gru", 1, kPinnedPitchGru}, {T_PGRU, "phone.gru", 1, kPinnedPhoneGru},
+    {T_VQ, "phone.vq", 1, kDealt, T_COUNT, true}, {T_TAIL1, "wave.tail1", 1, kDealt, T_TAIL1S, true}, {T_TAIL2, "wave.tail2", 1, kDealt, T_TAIL2S, true},
+    {T_TAIL3, "wave.tail3", 1, kDealt, T_COUNT, true}, {T_BLKA1, "wave.blk.a", 1, kPinned}, {T_BLKA2, "wave.blk.a", 1, kPinned},
+    {T_BLKA4, "wave.blk.a", 1, kPinned}, {T_BLKA8, "wave.blk.a", 1, kPinned}, {T_BLKB, "wave.blk.b", 4, kPinned}, {T_BLKBQ, "wave.blk.bq", 4, kPinned},
+    {T_F4S, "phone.f4", 1, kPinned}, {T_F5S, "phone.f5", 1, kPinned}, {T_RBS, "phone.rb", 4, kPinned}, {T_P1S, "pitch.p1", 1, kPinned},
+    {T_UP1S, "wave.up1", 1, kPinned}, {T_TAIL1S, "wave.tail1", 1, kDealt, T_COUNT, true}, {T_TAIL2S, "wave.tail2", 1, kDealt, T_COUNT, true},
+    {T_QGRU1, "pitch.gru", 1, kPinnedPitchGru}, {T_PGRU1, "phone.gru", 1, kPinnedPhoneGru}, {T_QGRUM, "pitch.gru", 2, kPinnedPitchGru}, {T_PGRUM, "phone.gru", 2, kPinnedPhoneGru}};
+constexpr bool bodies_in_order() {
+  for (int i = 0; i < T_COUNT; ++i) {
+    const Body& b = kBodies[i], & s = kBodies[b.sparse];
+    if (b.type != i || s.sparse != s.type || s.cap != b.cap || s.place != b.place || (b.spread && b.place != kDealt)) return false;
+  }
+  return true;
+}
+static_assert(sizeof(kBodies) / sizeof(kBodies[0]) == T_COUNT && bodies_in_order(), "kBodies: one entry per BodyType, in the enum's order; a sparse form is placed like its full one");
+static_assert(T_COUNT <= 64, "TableBuilder::only, BeatriceBatchMeas_TickOnlyTypes: a type is a bit of a 64-bit mask");
+// a row of Ops<H>::L: the kernel body that runs type T at H hops per step
+template <BodyType T, class Op> struct Row { static constexpr BodyType type = T; using op = Op; };
+
 // The bodies of a tick with H hops per stage (H = 1: a step is one 10 ms hop of every stream; H = 2: two -- every stage then
 // works on twice the rows per weight fragment and per launch, and a launch's fixed costs are paid once per two hops; the two
 // recurrent layers run their two hops one after the other inside a workgroup).  Same layer types as the in-order chain at H hops
@@ -145,18 +185,25 @@ struct Ops {
   using GruQm = std::conditional_t<H <= 2, rc::NopOp, rc::GruRowsOp<128, 128, 3>>;
   using GruPm = std::conditional_t<H <= 2, rc::NopOp, rc::GruRowsOp<256, 256, 3>>;
   using Vq = std::conditional_t<H == 1, VqOp, VqRowsOp<H>>;   // (several hops: a stream's rows in one workgroup, the codebook read once)
-  template <class... Ms> struct List { using Tab = fuse::Table<Ms...>; using Builder = fuse::TableBuilder<Ms...>; };
+  // The type list of the table kernels, in the enum's order (checked): position = BodyType = the type's bit in the measurement masks
+  template <class... Rs> struct List {
+    template <int... Is> static constexpr bool in_order(std::integer_sequence<int, Is...>) { return ((Rs::type == Is) && ...); }
+    static_assert(sizeof...(Rs) == T_COUNT && in_order(std::make_integer_sequence<int, sizeof...(Rs)>{}), "Ops<H>::L: one Row per BodyType, in the enum's order");
+    using Tab = fuse::Table<fuse::Many<typename Rs::op, kBodies[Rs::type].cap>...>;
+    using Builder = fuse::TableBuilder<fuse::Many<typename Rs::op, kBodies[Rs::type].cap>...>;
+    template <BodyType T> using Op = typename std::tuple_element_t<T, std::tuple<Rs...>>::op;
+  };
   using L = List<
-      fuse::Many<F1Op2, 1>, fuse::Many<FftOp2, 1>, fuse::Many<OpF2, 1>, fuse::Many<OpF3, 1>, fuse::Many<OpF4, 1>, fuse::Many<OpF5, 1>,
-      fuse::Many<OpP1, 1>, fuse::Many<OpRB, 4>, fuse::Many<OpP23, 2>, fuse::Many<OpPOUT, 1>, fuse::Many<HeadOp8, 1>,
-      fuse::Many<OpOUT, 1>, fuse::Many<CondOp2, 1>, fuse::Many<OpINP, 1>, fuse::Many<OpUP1, 1>, fuse::Many<OpRES1A, 1>,
-      fuse::Many<OpRES1B, 1>, fuse::Many<OpUP2, 1>, fuse::Many<GruQ, 1>, fuse::Many<GruP, 1>,
-      fuse::Many<Vq, 1>, fuse::Many<T1, 1>, fuse::Many<T2, 1>, fuse::Many<T3, 1>, fuse::Many<rc::BlockAOp<1, H>, 1>, fuse::Many<rc::BlockAOp<2, H>, 1>,
-      fuse::Many<rc::BlockAOp<4, H>, 1>, fuse::Many<rc::BlockAOp<8, H>, 1>, fuse::Many<rc::BlockBOpH<H>, 4>, fuse::Many<rc::BlockBqOpH<H>, 4>,
-      fuse::Many<OpF4s, 1>, fuse::Many<OpF5s, 1>, fuse::Many<OpRBs, 4>, fuse::Many<OpP1s, 1>, fuse::Many<OpUP1s, 1>, fuse::Many<T1s, 1>, fuse::Many<T2s, 1>,
-      fuse::Many<GruQ1, 1>, fuse::Many<GruP1, 1>, fuse::Many<GruQm, 2>, fuse::Many<GruPm, 2>>;
+      Row<T_F1, F1Op2>, Row<T_FFT, FftOp2>, Row<T_F2, OpF2>, Row<T_F3, OpF3>, Row<T_F4, OpF4>, Row<T_F5, OpF5>, Row<T_P1, OpP1>, Row<T_RB, OpRB>,
+      Row<T_P23, OpP23>, Row<T_POUT, OpPOUT>, Row<T_HEAD, HeadOp8>, Row<T_OUT, OpOUT>, Row<T_COND, CondOp2>, Row<T_INP, OpINP>, Row<T_UP1, OpUP1>,
+      Row<T_RES1A, OpRES1A>, Row<T_RES1B, OpRES1B>, Row<T_UP2, OpUP2>, Row<T_QGRU, GruQ>, Row<T_PGRU, GruP>, Row<T_VQ, Vq>, Row<T_TAIL1, T1>,
+      Row<T_TAIL2, T2>, Row<T_TAIL3, T3>, Row<T_BLKA1, rc::BlockAOp<1, H>>, Row<T_BLKA2, rc::BlockAOp<2, H>>, Row<T_BLKA4, rc::BlockAOp<4, H>>,
+      Row<T_BLKA8, rc::BlockAOp<8, H>>, Row<T_BLKB, rc::BlockBOpH<H>>, Row<T_BLKBQ, rc::BlockBqOpH<H>>, Row<T_F4S, OpF4s>, Row<T_F5S, OpF5s>,
+      Row<T_RBS, OpRBs>, Row<T_P1S, OpP1s>, Row<T_UP1S, OpUP1s>, Row<T_TAIL1S, T1s>, Row<T_TAIL2S, T2s>, Row<T_QGRU1, GruQ1>, Row<T_PGRU1, GruP1>,
+      Row<T_QGRUM, GruQm>, Row<T_PGRUM, GruPm>>;
   using Tab = typename L::Tab;
   using Builder = typename L::Builder;
+  template <BodyType T> using Op = typename L::template Op<T>;
 };
 
 // Stage of each body.  Front end: the in-order chain's launch order, the pitch estimator zipped into the content
@@ -195,13 +242,9 @@ struct State {
   // occupied a body confined to half the chip leaves the other half idle (a 20-step run: 3.78 -> 3.51 M frames/s with the halves everywhere)
   DevBuf<fuse::WgDesc> d_desc_plain;
   int table_total_plain = 0;
-  // ... and the same order with the workgroups of EMPTY stages left out, for the two shapes a fill and a drain go through: stages
-  // 0 .. k occupied (range_off[0][k]) and stages k .. last occupied (range_off[1][k]).  A partly filled launch otherwise dispatches
-  // every stage's workgroups only for most of them to leave at once -- thousands of slot turns per launch in a run of few steps.
-  // One buffer; n = 0: not built (very large batches) or the tick's occupied stages are no such range -> the plain list.
+  // ... and the same order with the workgroups of EMPTY stages left out, for a fill's and a drain's shapes (fuse::RangeLists); one buffer
   DevBuf<fuse::WgDesc> d_desc_ranges;
-  size_t range_off[2][kMaxStages] = {};
-  int range_n[2][kMaxStages] = {};
+  fuse::RangeIndex range;
   DevBuf<unsigned long long> d_trace;     // BEATRICE_HIP_TICK_TRACE=<file>: per-workgroup timeline of the last full tick
   bool table_dirty = true;
   DevBuf<unsigned char> d_snap;     // [kRing][snap_bytes] settings snapshots

@@ -9,7 +9,10 @@ import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-TYPES = ["T_F1", "T_FFT", "T_HEAD", "T_COND", "T_VQ", "T_F2L", "T_F3L", "T_P23L", "T_POUTL", "T_OUTL", "T_INPL", "T_UP1L", "T_RES1AL", "T_RES1BL", "T_UP2L"]
+# tick::BodyType, in order, from the header's enum block
+ENUM = re.search(r"enum BodyType \{(.*?)\};", open(os.path.join(REPO, "beatrice-vst_amd", "csrc", "tick.hip.h")).read(), re.S).group(1)
+NAMES = [n.strip() for n in ENUM.replace("\n", " ").split(",") if n.strip()]
+TYPES = [n for n in NAMES if n != "T_COUNT"]
 SRC = r'''
 #include <algorithm>
 #include <cmath>
@@ -52,9 +55,7 @@ def main():
         if r.returncode:
             print(r.stderr[-3000:])
             sys.exit(1)
-    # enum values of the types, from tick.hip.h
-    enum = re.search(r"enum BodyType \{(.*?)\};", open(os.path.join(REPO, "beatrice-vst_amd", "csrc", "tick.hip.h")).read(), re.S).group(1)
-    names = [n.strip() for n in enum.replace("\n", " ").split(",") if n.strip()]
+    names = NAMES
     cur = None
     rows = {}
     for line in r.stderr.splitlines():

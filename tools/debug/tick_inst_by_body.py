@@ -5,7 +5,7 @@ Under `rocprofv3 --pmc ... --kernel-trace` the table-kernel dispatches of a grou
 (tools/debug/tick_inst_by_body.sh cuts them); without a profiler the script prints the group's own launch time.
   python tools/debug/tick_inst_by_body.py [streams] [hops per step]
 """
-import ctypes, importlib, os, sys, tempfile
+import ctypes, importlib, os, re, sys, tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tools"))
 import torch
@@ -13,9 +13,9 @@ torch.cuda.init()
 import make_model
 bv = importlib.import_module("beatrice-vst_amd")
 
-# tick::BodyType (csrc/tick.hip.h), in order
-TYPES = ("F1 FFT F2 F3 F4 F5 P1 RB P23 POUT HEAD OUT COND INP UP1 RES1A RES1B UP2 QGRU PGRU VQ TAIL1 TAIL2 TAIL3 "
-         "BLKA1 BLKA2 BLKA4 BLKA8 BLKB BLKBQ F4S F5S RBS P1S UP1S TAIL1S TAIL2S QGRU1 PGRU1 QGRUM PGRUM").split()
+# tick::BodyType, in order, from the header's enum block (without the T_ prefix and T_COUNT)
+_ENUM = re.search(r"enum BodyType \{(.*?)\};", open(os.path.join(REPO, "beatrice-vst_amd", "csrc", "tick.hip.h")).read(), re.S).group(1)
+TYPES = [n.strip()[2:] for n in _ENUM.replace("\n", " ").split(",") if n.strip() and n.strip() != "T_COUNT"]
 GROUPS = [("all", None), ("f1", ["F1"]), ("fft", ["FFT"]), ("f2", ["F2"]), ("f3", ["F3"]), ("f4", ["F4"]), ("f5", ["F5"]), ("p1", ["P1"]),
           ("rb x4", ["RB"]), ("p23 x2", ["P23"]), ("pout", ["POUT"]), ("head", ["HEAD"]), ("out", ["OUT"]), ("cond", ["COND"]), ("inp", ["INP"]),
           ("up1", ["UP1"]), ("res1a", ["RES1A"]), ("res1b", ["RES1B"]), ("up2", ["UP2"]), ("qgru", ["QGRU", "QGRU1", "QGRUM"]), ("pgru", ["PGRU", "PGRU1", "PGRUM"]),
