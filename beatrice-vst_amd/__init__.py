@@ -467,6 +467,10 @@ _BATCH = {
     "BeatriceBatch_ExportStreamsInFlight": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
     "BeatriceBatch_ImportStreamsInFlight": (C.c_int, [_vp, C.c_int, _i32p, _vp, _i32p, C.c_int]),
     "BeatriceBatch_MoveStreamsInFlight": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, C.c_int]),
+    "BeatriceBatch_Stream48kQuiescent": (C.c_int, [_vp, C.c_int]),
+    "BeatriceBatch_ExportStreams48kInFlight": (C.c_int, [_vp, C.c_int, _i32p, _vp]),
+    "BeatriceBatch_ImportStreams48kInFlight": (C.c_int, [_vp, C.c_int, _i32p, _vp, _i32p, C.c_int]),
+    "BeatriceBatch_MoveStreams48kInFlight": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, C.c_int]),
     "BeatriceBatch_ConvertFrames": (C.c_int, [_vp, _f32p, _f32p]),
     "BeatriceBatch_ConvertFramesDevice": (C.c_int, [_vp, _vp, _vp]),
     "BeatriceBatch_ConvertBlocks48k": (C.c_int, [_vp, _f32p, _f32p, C.c_int]),
@@ -679,6 +683,43 @@ class Batch:
         em = None if entry_map is None else np.ascontiguousarray(entry_map, np.int32).reshape(-1)
         self._check(self.a.BeatriceBatch_MoveStreamsInFlight(self.h, dst.h, len(idx), iptr(idx), iptr(to),
                                                              None if em is None else iptr(em), 0 if em is None else len(em)))
+
+    def stream48k_quiescent(self, stream):
+        """Around the resident 48 kHz blocks (BeatriceBatch_BindResidentIO48k): True when no step the stream took part in is inside
+        the pipeline AND the wrapper launch that emits its last block has been enqueued (BeatriceBatch_Stream48kQuiescent), which is
+        when the in-flight calls below take it: one call later than stream_quiescent in plain tick mode."""
+        rc = int(self.a.BeatriceBatch_Stream48kQuiescent(self.h, int(stream)))
+        if rc < 0:
+            raise RuntimeError("BeatriceBatch_Stream48kQuiescent failed: %d" % rc)
+        return rc == 1
+
+    def export_streams48k_in_flight(self, streams):
+        """export_streams_in_flight for a batch bound to resident 48 kHz blocks (BeatriceBatch_ExportStreams48kInFlight): the same
+        bytes, the 48 kHz wrapper's state of the stream among them.  Not for an audio thread."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        buf = C.create_string_buffer(max(1, len(idx) * self.stream_blob_bytes()))
+        self._check(self.a.BeatriceBatch_ExportStreams48kInFlight(self.h, len(idx), iptr(idx), C.cast(buf, _vp)))
+        return buf.raw[:len(idx) * self.stream_blob_bytes()]
+
+    def import_streams48k_in_flight(self, streams, blobs, entry_map=None):
+        """import_streams_in_flight for a batch bound to resident 48 kHz blocks (BeatriceBatch_ImportStreams48kInFlight)."""
+        idx = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if len(blobs) != len(idx) * self.stream_blob_bytes():
+            raise ValueError("import_streams48k_in_flight: %d bytes for %d streams of %d bytes each" % (len(blobs), len(idx), self.stream_blob_bytes()))
+        em = None if entry_map is None else np.ascontiguousarray(entry_map, np.int32).reshape(-1)
+        buf = C.create_string_buffer(bytes(blobs), max(1, len(blobs)))
+        self._check(self.a.BeatriceBatch_ImportStreams48kInFlight(self.h, len(idx), iptr(idx), C.cast(buf, _vp),
+                                                                  None if em is None else iptr(em), 0 if em is None else len(em)))
+
+    def move_streams48k_in_flight(self, dst, streams, dst_streams, entry_map=None):
+        """move_streams_in_flight between two batches bound to resident 48 kHz blocks on one device
+        (BeatriceBatch_MoveStreams48kInFlight): the stream's next block in `dst` is the block it would have got here."""
+        idx, to = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (streams, dst_streams))
+        if len(idx) != len(to):
+            raise ValueError("move_streams48k_in_flight: %d source streams, %d destination streams" % (len(idx), len(to)))
+        em = None if entry_map is None else np.ascontiguousarray(entry_map, np.int32).reshape(-1)
+        self._check(self.a.BeatriceBatch_MoveStreams48kInFlight(self.h, dst.h, len(idx), iptr(idx), iptr(to),
+                                                                None if em is None else iptr(em), 0 if em is None else len(em)))
 
     def set_stream_rate(self, stream, rate):
         """One stream's SetSampleRate (BeatriceBatch_SetStreamRate): its resampler pair and FIFO restart at `rate`, its gains keep

@@ -172,7 +172,7 @@ struct BeatriceBatch {
     PinnedBuf<unsigned char> h_stage;
     DevBuf<unsigned char> d_stage;
   } sb;
-  // BeatriceBatch_StreamQuiescent / ExportStreamsInFlight / ImportStreamsInFlight / MoveStreamsInFlight (stream_move_plan.h): which streams
+  // BeatriceBatch_StreamQuiescent / ExportStreamsInFlight / ImportStreamsInFlight / MoveStreamsInFlight and their 48k siblings of mode F (stream_move_plan.h): which streams
   // have a step inside the tick pipeline (marked by tick_run, cleared at every drained point); the event behind an in-flight export's
   // copy; the pinned staging of the in-flight imports, a ring of two CALLS (an entry holds all the blobs of its call and grows with it;
   // its event: the call's last scatter has run); the two events of a move between batches on different streams -- the source batch's own
@@ -1471,14 +1471,15 @@ int BeatriceBatch_ResetStream(BeatriceBatch* b, int stream) {
   if (!ok) return -2;
   return BeatriceBatch_FlushSpeaker(b, stream);
 }
-// The same as a per-stream setting that travels with the next step (beatrice_batch.h; tick_reset.hip.h): in plain tick mode and in host
-// streaming nothing drains -- the stream is marked, its key/value blocks are installed as BeatriceBatch_FlushSpeaker does, and tick_run
-// carries the reset through the stages with the step it applies to.  Every other mode: BeatriceBatch_ResetStream.
+// The same as a per-stream setting that travels with the next step (beatrice_batch.h; tick_reset.hip.h): in plain tick mode, in host
+// streaming and around the resident 48 kHz blocks (mode F) nothing drains -- the stream is marked, its key/value blocks are installed as
+// BeatriceBatch_FlushSpeaker does, and tick_run carries the reset through the stages with the step it applies to (in F also through the
+// wrapper's two halves, batch_tick.hip.h tick_reset_wrap48).  Every other mode: BeatriceBatch_ResetStream.
 int BeatriceBatch_ResetStreamInFlight(BeatriceBatch* b, int stream) {
   BATCH_OPEN(b);
   if (stream < -1 || stream >= b->B) return -1;
   const modes::Mode mode = modes::mode_of(flags_of(b));
-  if (mode != modes::Mode::D && mode != modes::Mode::E) return BeatriceBatch_ResetStream(b, stream);
+  if (mode != modes::Mode::D && mode != modes::Mode::E && mode != modes::Mode::F) return BeatriceBatch_ResetStream(b, stream);
   if (!tick_reset_prepare(b)) return -2;
   for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? b->B : stream + 1); ++s) b->tk.reset_pending[s] = 1;
   b->tk.any_reset_pending = true;
@@ -1671,8 +1672,9 @@ int BeatriceBatch_ImportStreams(BeatriceBatch* b, int n, const int* streams, con
 // stream between two ticks, touches state nobody else reads or writes.  Each stream is taken, and turned, at its OWN counter.
 namespace {
 struct MoveSide : smove::Side {   // one batch's part of a call
-  MoveSide(const BeatriceBatch* b, int n_, const int* streams_, bool pointers_ok_) {
-    plain_tick = modes::mode_of(flags_of(b)) == modes::Mode::D;
+  MoveSide(const BeatriceBatch* b, int n_, const int* streams_, bool pointers_ok_, smove::Rule rule_ = smove::kRulePlain) {
+    const modes::Mode mode = modes::mode_of(flags_of(b));
+    plain_tick = mode == modes::Mode::D; around48k = mode == modes::Mode::F; rule = rule_;
     B = b->B; n = n_; streams = streams_; pointers_ok = pointers_ok_;
   }
 };
@@ -1684,21 +1686,48 @@ smove::Verdict move_at_rest(const BeatriceBatch* b, const smove::Side& s, bool i
 int move_own_counter(const BeatriceBatch* b, int s) { return smove::own_counter(b->tk.ragged, b->tk.hop_s, s, b->hop_host); }
 }  // namespace
 
-int BeatriceBatch_StreamQuiescent(const BeatriceBatch* b, int stream) {
-  if (!b || !b->ok || modes::mode_of(flags_of(b)) != modes::Mode::D || stream < 0 || stream >= b->B) return -1;
-  return b->mv.seen.quiescent(stream, b->tk.tick, b->tk.plan.count()) ? 1 : 0;
+namespace {
+// (the four calls of mode D and the four of mode F are one body each: what differs is the mode asked for and the rule asked, both in MoveSide)
+int stream_quiescent(const BeatriceBatch* b, int stream, smove::Rule rule) {
+  if (!b || !b->ok || modes::mode_of(flags_of(b)) != (rule == smove::kRuleAround48k ? modes::Mode::F : modes::Mode::D) || stream < 0 || stream >= b->B) return -1;
+  return smove::quiescent(b->mv.seen, rule, stream, b->tk.tick, b->tk.plan.count()) ? 1 : 0;
+}
+int export_streams_in_flight(BeatriceBatch* b, int n, const int* streams, void* blobs, smove::Rule rule);
+int import_streams_in_flight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map, smove::Rule rule);
+int move_streams_in_flight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams, const int* entry_map, int n_map, smove::Rule rule);
+}  // namespace
+
+int BeatriceBatch_StreamQuiescent(const BeatriceBatch* b, int stream) { return stream_quiescent(b, stream, smove::kRulePlain); }
+int BeatriceBatch_ExportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, void* blobs) { return export_streams_in_flight(b, n, streams, blobs, smove::kRulePlain); }
+int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
+  return import_streams_in_flight(b, n, streams, blobs, entry_map, n_map, smove::kRulePlain);
+}
+int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
+                                      const int* entry_map, int n_map) {
+  return move_streams_in_flight(src, dst, n, src_streams, dst_streams, entry_map, n_map, smove::kRulePlain);
+}
+// ---- ... and between two batches that both go on converting resident 48 kHz blocks (mode F; beatrice_batch.h footnote (14)) ------------
+// The same calls with the second quiescence rule (stream_move_plan.h kRuleAround48k): the wrapper's output half runs one launch behind the
+// step's last stage, so a stream is at rest one launch later than in D.  The blob and the piece table already hold its Wrap48State.
+int BeatriceBatch_Stream48kQuiescent(const BeatriceBatch* b, int stream) { return stream_quiescent(b, stream, smove::kRuleAround48k); }
+int BeatriceBatch_ExportStreams48kInFlight(BeatriceBatch* b, int n, const int* streams, void* blobs) { return export_streams_in_flight(b, n, streams, blobs, smove::kRuleAround48k); }
+int BeatriceBatch_ImportStreams48kInFlight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
+  return import_streams_in_flight(b, n, streams, blobs, entry_map, n_map, smove::kRuleAround48k);
+}
+int BeatriceBatch_MoveStreams48kInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
+                                         const int* entry_map, int n_map) {
+  return move_streams_in_flight(src, dst, n, src_streams, dst_streams, entry_map, n_map, smove::kRuleAround48k);
 }
 
-int BeatriceBatch_ExportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, void* blobs) {
+namespace {
+int export_streams_in_flight(BeatriceBatch* b, int n, const int* streams, void* blobs, const smove::Rule rule) {
   BATCH_OPEN(b);
-  const MoveSide side(b, n, streams, blobs != nullptr);
+  const MoveSide side(b, n, streams, blobs != nullptr, rule);
   if (smove::args(side) != smove::kGo) return -1;
   if (move_at_rest(b, side, true) != smove::kGo) return -3;
   if (!blob_prepare(b, n) || (!b->mv.ev_export && !b->mv.ev_export.create("export event"))) return -2;
   return export_rounds(b, n, streams, blobs, true);
 }
-
-namespace {
 // the rings of an in-flight import: the blobs into the call's pinned staging entry, up and scattered round by round on the batch's stream,
 // each stream turned to its own counter; nothing is waited for but the entry's previous user
 int import_rounds_in_flight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const std::vector<Taken>& taken) {
@@ -1732,11 +1761,10 @@ int import_rounds_in_flight(BeatriceBatch* b, int n, const int* streams, const v
   b->mv.imports += 1;
   return 0;
 }
-}  // namespace
 
-int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map) {
+int import_streams_in_flight(BeatriceBatch* b, int n, const int* streams, const void* blobs, const int* entry_map, int n_map, const smove::Rule rule) {
   BATCH_OPEN(b);
-  const MoveSide side(b, n, streams, blobs != nullptr && n_map >= 0 && (entry_map == nullptr) == (n_map == 0));
+  const MoveSide side(b, n, streams, blobs != nullptr && n_map >= 0 && (entry_map == nullptr) == (n_map == 0), rule);
   if (smove::args(side) != smove::kGo) return -1;
   std::vector<Taken> taken;
   if (!blobs_take(b, n, blobs, entry_map, n_map, &taken)) return -1;
@@ -1746,8 +1774,6 @@ int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* stre
   blobs_settle(b, n, streams, taken);
   return 0;
 }
-
-namespace {
 // the settings part of a move, host to host, with the checks the blob path makes
 bool move_take(const BeatriceBatch* src, const BeatriceBatch* dst, int n, const int* src_streams, const int* entry_map, int n_map, std::vector<Taken>* taken) {
   taken->resize(n);
@@ -1793,16 +1819,15 @@ int move_rings_fenced(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* 
          hip_ok(hipStreamWaitEvent(src->stream, dst->mv.ev_dst, 0), "source waits for the move") && ok;
   return ok ? 0 : -2;
 }
-}  // namespace
 
-int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
-                                      const int* entry_map, int n_map) {
+int move_streams_in_flight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams, const int* entry_map, int n_map,
+                           const smove::Rule rule) {
   if (!src || !dst || src == dst) return -1;
   if (!src->ok || !dst->ok) return -2;
   if (src->device != dst->device) return -1;
   const DeviceScope dev_(dst->device);
   const bool map_ok = n_map >= 0 && (entry_map == nullptr) == (n_map == 0);
-  const MoveSide from(src, n, src_streams, map_ok), to(dst, n, dst_streams, map_ok);
+  const MoveSide from(src, n, src_streams, map_ok, rule), to(dst, n, dst_streams, map_ok, rule);
   if (smove::args(from) != smove::kGo || smove::args(to) != smove::kGo || !sblob::same_layout(src->sb.layout, dst->sb.layout)) return -1;
   std::vector<Taken> taken;
   if (!move_take(src, dst, n, src_streams, entry_map, n_map, &taken)) return -1;
@@ -1812,6 +1837,7 @@ int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, in
   blobs_settle(dst, n, dst_streams, taken);
   return 0;
 }
+}  // namespace
 
 // ---- per-hop ------------------------------------------------------------------------------------
 int BeatriceBatch_ConvertFramesDevice(BeatriceBatch* b, const float* d_in, float* d_out) {

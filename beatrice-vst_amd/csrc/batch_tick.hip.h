@@ -318,6 +318,11 @@ struct HostProf {
 //           tail                       its three parts (YB2 YC2 | YA3 YB3 YC3 | YA4 YB4 YC4) before the tail stage that owns them, whole;
 //                                      the sub-steps' carried frames live in LDS
 //           ya3, ya4                   nothing                       -- their two-frame histories are TS_YA3 / TS_YA4 of the tail block
+//   wrapper (mode F) Wrap48State   hist_in before the WRAPPER launch of tick k (its input half reads step k), whole; ztail and fpend
+//                                      before the wrapper launch that runs step k's output half -- the one in front of tick k + stages, or
+//                                      the flush launch of a drain -- whole.  Every form of wrap48_tick_kernel reads a stream's state
+//                                      once when a launch starts and writes it once when it ends, so a clear between two launches is exact
+constexpr int kResetWrapIn = -2, kResetWrapOut = -3;   // (in the place of a stage in State::reset_stage)
 static bool tick_reset_prepare(BeatriceBatch* b) {
   using namespace tick;
   State& k = b->tk;
@@ -364,6 +369,21 @@ static bool tick_reset_prepare(BeatriceBatch* b) {
     std::fprintf(stderr, "beatrice_hip: the in-flight reset table does not cover the batch's rings\n");
     return false;
   }
+  // The 48 kHz wrapper around the ticks (mode F): the three parts of Wrap48State, each whole.  They belong to no stage of the tick: the
+  // input half's history is cleared in front of the wrapper launch of the step's own tick, the output half's two parts in front of the
+  // wrapper launch ONE LAUNCH BEHIND the step's last stage (tick_reset_wrap48 below; neither sentinel is a stage tick_reset_launch meets)
+  const int wrap_first = (int)rings.size();
+  {
+    float* w = reinterpret_cast<float*>(b->d_w48.get());
+    const unsigned stride = (unsigned)(sizeof(Wrap48State) / sizeof(float));
+    const size_t part[3] = {offsetof(Wrap48State, hist_in), offsetof(Wrap48State, ztail), offsetof(Wrap48State, fpend)};
+    const unsigned len[3] = {30u, 16u, 240u};
+    static_assert(sizeof(Wrap48State) == sizeof(float) * (30 + 16 + 240), "the in-flight reset clears every part of Wrap48State");
+    for (int i = 0; i < 3; ++i) {
+      rings.push_back(ResetRing{w + part[i] / sizeof(float), stride, len[i], 1});
+      stage.push_back(i == 0 ? kResetWrapIn : kResetWrapOut); spare.push_back(0);
+    }
+  }
   DevBuf<ResetRing> d_rings;
   DevBuf<float> keep;
   StagedRing<int> list;
@@ -375,6 +395,7 @@ static bool tick_reset_prepare(BeatriceBatch* b) {
       !keep.alloc((size_t)b->B * (256 + 128), "reset gru keep", false) || !list.alloc(State::kResetStaging, list_ints, "reset work list"))
     return false;
   k.n_reset_rings = (int)rings.size(); k.d_reset_rings = std::move(d_rings); k.reset_stage = std::move(stage); k.reset_spare = std::move(spare);
+  k.reset_wrap_first = wrap_first;
   k.reset_m.clear();
   for (const ResetRing& r : rings) k.reset_m.push_back(r.m);
   k.d_gru_keep = std::move(keep); k.reset_list = std::move(list); k.reset_list_ints = list_ints;
@@ -397,7 +418,7 @@ static bool tick_reset_launch(BeatriceBatch* b, hipStream_t st) {
   for (const State::Travelling& r : k.resets) {
     const int d = (int)(k.tick - r.tick);   // the stage the reset's step reaches in this tick
     if (d < n_stages) k.resets[keep_n++] = r;
-    if (d >= n_stages) continue;
+    if (d >= n_stages) continue;   // (mode F: its last clear went in front of this tick's wrapper launch, tick_reset_wrap48)
     for (int i = 0; i < k.n_reset_rings; ++i) {
       if (k.reset_stage[i] != d) continue;
       if (!claim()) return false;
@@ -434,14 +455,48 @@ static bool tick_reset_launch(BeatriceBatch* b, hipStream_t st) {
   k.reset_launches += 1;
   return hip_ok(hipGetLastError(), "in-flight reset");
 }
-// The drained form of a reset for the streams still waiting for their step (leaving tick mode: the in-order chain takes the batch over)
+// Mode F, in front of a launch of the 48 kHz wrapper (the one of tick k.tick, or -- `flush` -- the one a drain sends behind the last
+// tick): the parts of Wrap48State the travelling resets need cleared before it.  A reset whose step was fed by tick r.tick clears the
+// input half's history before the wrapper launch of that very tick, and the output half's tail and FIFO before the wrapper launch that
+// follows tick r.tick + stages - 1, the one that emits the step's block.  That is one launch behind the step's last stage: a reset stays
+// in the list until tick_reset_launch of tick r.tick + stages drops it, or the flush does.  Nothing is launched where no reset is due.
+static bool tick_reset_wrap48(BeatriceBatch* b, hipStream_t st, const bool flush) {
+  using namespace tick;
+  State& k = b->tk;
+  if (k.resets.empty() || k.reset_wrap_first < 0) return true;
+  const int n_stages = k.plan.count();
+  int n_items = 0;
+  int* list = nullptr;
+  size_t keep_n = 0;
+  for (const State::Travelling& r : k.resets) {
+    const long long d = k.tick - r.tick;
+    const bool in_half = !flush && d == 0, out_half = d == n_stages;
+    if (!flush || d < n_stages) k.resets[keep_n++] = r;   // (behind the flush no tick follows that would drop it, and the next tick has the same number)
+    if (!in_half && !out_half) continue;
+    if (!list && !(list = k.reset_list.claim((int)(k.reset_serial % State::kResetStaging)))) return false;
+    for (int i = k.reset_wrap_first; i < k.n_reset_rings; ++i) {
+      if (k.reset_stage[i] != (in_half ? kResetWrapIn : kResetWrapOut)) continue;
+      const ResetItem it{i, r.stream, -1, 0};
+      std::memcpy(list + 4 * (size_t)n_items++, &it, sizeof(it));
+    }
+  }
+  k.resets.resize(keep_n);
+  if (!list) return true;
+  hipLaunchKernelGGL(ring_reset_kernel, dim3(n_items), dim3(256), 0, st, k.d_reset_rings.get(), k.n_reset_rings, reinterpret_cast<const ResetItem*>(list), b->B);
+  if (!k.reset_list.mark((int)(k.reset_serial % State::kResetStaging), st)) return false;
+  k.reset_serial += 1;
+  return hip_ok(hipGetLastError(), "in-flight reset of the 48 kHz wrapper");
+}
+// The drained form of a reset for the streams still waiting for their step (leaving tick mode: the in-order chain takes the batch over;
+// out of mode F the stream's wrapper state with the rest, as BeatriceBatch_ResetStream clears it)
 static bool tick_reset_settle(BeatriceBatch* b) {
   tick::State& k = b->tk;
   bool ok = true;
   for (int s = 0; s < (int)k.reset_pending.size() && ok && k.any_reset_pending; ++s) {
     if (!k.reset_pending[s]) continue;
     ok = b->phone.arena.zero_stream(s, b->stream) && b->pitch.arena.zero_stream(s, b->stream) && b->wave.arena.zero_stream(s, b->stream) &&
-         hip_ok(hipMemsetAsync(b->pitch.d_prev_q + s, 0, sizeof(int), b->stream), "prev_q");
+         hip_ok(hipMemsetAsync(b->pitch.d_prev_q + s, 0, sizeof(int), b->stream), "prev_q") &&
+         (!b->r48.on || hip_ok(hipMemsetAsync(b->d_w48 + s, 0, sizeof(Wrap48State), b->stream), "w48 reset"));
   }
   std::fill(k.reset_pending.begin(), k.reset_pending.end(), 0);
   k.any_reset_pending = false;
@@ -595,6 +650,7 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
       wa.in48_post = r.d_in48 + (size_t)r.deferred_slot * b->B * b->H * r.channels * 480;
       r.deferred_slot = -1;
     }
+    if (!k.resets.empty() && !tick_reset_wrap48(b, st, false)) return false;   // (behind the wrapper launch before, in front of this one)
     hipLaunchKernelGGL(wrap48_tick_kernel, dim3(wrap48_tick_grid(wa)), dim3(256), 0, st, wa);
   }
   prof.lap(3);
@@ -720,8 +776,9 @@ bool tick_drain(BeatriceBatch* b) {
     wa.hv_post = r.deferred_step >= 0 && b->tk.step_ragged[r.deferred_step % tick::kRing] ? b->tk.d_hopv + (size_t)(r.deferred_step % tick::kRing) * b->tk.row : nullptr;
     wa.in48_post = r.d_in48 + (size_t)r.deferred_slot * b->B * b->H * r.channels * 480;
     r.deferred_slot = -1;
+    ok = b->tk.resets.empty() || tick_reset_wrap48(b, b->stream, true);   // (a reset whose step is the one this launch emits)
     hipLaunchKernelGGL(wrap48_tick_kernel, dim3(wrap48_tick_grid(wa)), dim3(256), 0, b->stream, wa);
-    ok = hip_ok(hipGetLastError(), "wrap48 flush");
+    ok = ok && hip_ok(hipGetLastError(), "wrap48 flush");
   }
   // every model hop that entered the pipeline has left it: the output halves still owed, in order.  With several hops per step
   // the hops of a step that is not full yet have not entered: the calls that end on them stay owed until later calls fill the

@@ -284,6 +284,7 @@ struct State {
   std::vector<int> reset_stage;               // [n_reset_rings] cleared before this stage's tick of the step
   std::vector<unsigned char> reset_spare;     // [n_reset_rings] ... but for the slot the step itself has written
   std::vector<int> reset_m;                   // [n_reset_rings] the ring's slot count
+  int reset_wrap_first = -1;                  // the rows of Wrap48State (hist_in, ztail, fpend; mode F, tick_reset_wrap48) are the table's last three
   static constexpr int kResetStaging = 8;
   StagedRing<int> reset_list;                 // [kResetStaging][reset_list_ints]: a tick's work list, read by the kernels in place
   size_t reset_list_ints = 0;

@@ -16,7 +16,12 @@
 //     The tick runs the cell on the old state; between ticks k + g and k + g + 1 -- before any reader of step k's state -- the cell
 //     of that stream is run again from a zero state (gru_restart_kernel: the tick's own cell body on a one-stream view of the rings,
 //     the previous frame saved, zeroed and put back around it);
-//   * outputs without history (read at the step's own frames only) need nothing.
+//   * outputs without history (read at the step's own frames only) need nothing;
+//   * around the resident 48 kHz blocks (mode F) the stream's Wrap48State belongs to no stage: the wrapper launch in front of tick k
+//     reads and writes the input half's history for step k, and the launch in front of tick k + stages (or the flush of a drain)
+//     runs step k's OUTPUT half -- one launch behind the step's last stage.  Each part is cleared whole in front of the wrapper launch
+//     that uses it for step k; every form of wrap48_tick_kernel holds the state in registers during a launch, so no body of it knows
+//     about resets (batch_tick.hip.h tick_reset_wrap48).  The 30 floats of the history go ring_reset_kernel's scalar way.
 // The (ring -> clear-before-stage, spare?) table is built in batch_tick.hip.h tick_reset_prepare.
 #pragma once
 
@@ -29,7 +34,8 @@ struct ResetItem { int ring, stream, spare, pad; };
 
 // One workgroup per (ring, stream) piece of the tick's work list; the list sits in PINNED HOST memory (a StagedRing entry written by
 // tick_run, like the per-stream counters of ragged steps), so the host may run ahead of the device.  16-byte stores wherever the piece
-// allows them (every ring does; the single word of the pitch head's previous bin goes the scalar way).
+// allows them (every ring does; the single word of the pitch head's previous bin goes the scalar way, and so do the parts of a
+// Wrap48State that are no multiple of four floats or, in every other stream's 1 144 bytes, do not start on a 16-byte boundary).
 static __global__ __launch_bounds__(256) void ring_reset_kernel(const ResetRing* __restrict__ rings, const int n_rings, const ResetItem* __restrict__ items, const int n_streams) {
   const ResetItem it = items[blockIdx.x];
   if (it.ring < 0 || it.ring >= n_rings || it.stream < 0 || it.stream >= n_streams) return;

@@ -186,17 +186,26 @@ def affine_speaker(rank, world, local_stream, n_speakers):
     return rank + world * (local_stream % mine)
 
 
+def _around_48k(batch):
+    """True when the batch converts resident 48 kHz blocks (BeatriceBatch_BindResidentIO48k): the one mode in which
+    BeatriceBatch_Stream48kQuiescent answers at all."""
+    ask = getattr(batch.a, "BeatriceBatch_Stream48kQuiescent", None)
+    return ask is not None and ask(batch.h, 0) >= 0
+
+
 def _move_streams_in_flight(src_batch, src_streams, dst_batch, dst_streams, entry_map, reset_source):
-    """move_streams(in_flight=True): both batches are in plain tick mode and go on ticking; the streams named are quiescent
-    (Batch.stream_quiescent).  On one device the rings go from batch to batch on the device and nothing is returned; across
-    devices the in-flight blob pair carries them and the blobs are returned."""
+    """move_streams(in_flight=True): both batches are in plain tick mode, or both convert resident 48 kHz blocks, and go on ticking;
+    the streams named are quiescent (Batch.stream_quiescent / Batch.stream48k_quiescent).  On one device the rings go from batch to
+    batch on the device and nothing is returned; across devices the in-flight blob pair carries them and the blobs are returned.
+    One batch in each of the two modes: the plain calls are asked and refuse."""
     a = src_batch.a
+    k48 = _around_48k(src_batch) and _around_48k(dst_batch)
     if a.BeatriceBatch_Device(src_batch.h) == dst_batch.a.BeatriceBatch_Device(dst_batch.h):
-        src_batch.move_streams_in_flight(dst_batch, src_streams, dst_streams, entry_map)
+        (src_batch.move_streams48k_in_flight if k48 else src_batch.move_streams_in_flight)(dst_batch, src_streams, dst_streams, entry_map)
         blobs = None
     else:
-        blobs = src_batch.export_streams_in_flight(src_streams)
-        dst_batch.import_streams_in_flight(dst_streams, blobs, entry_map)
+        blobs = (src_batch.export_streams48k_in_flight if k48 else src_batch.export_streams_in_flight)(src_streams)
+        (dst_batch.import_streams48k_in_flight if k48 else dst_batch.import_streams_in_flight)(dst_streams, blobs, entry_map)
     if reset_source:
         for s in src_streams:
             src_batch._check(a.BeatriceBatch_ResetStreamInFlight(src_batch.h, int(s)))
@@ -220,9 +229,11 @@ def move_streams(src_batch, src_streams, dst_batch, dst_streams, entry_map=None,
     Between ranks the blob is plain bytes: export_streams on the rank that has the stream, broadcast_bytes (or a
     point-to-point send of a uint8 tensor) to the rank that takes it, import_streams there.
 
-    in_flight: neither batch drains (both in plain tick mode, the streams quiescent): the device-to-device call when both batches
-    live on one device (returns None), the in-flight blob pair otherwise (returns the blobs); reset_source then marks the source
-    slots with BeatriceBatch_ResetStreamInFlight.  The any-rate wrapper's state does not travel this way: with_wrapper is refused."""
+    in_flight: neither batch drains (both in plain tick mode, or both bound to resident 48 kHz blocks -- then the 48 kHz wrapper's
+    state travels too; the streams quiescent): the device-to-device call when both batches live on one device (returns None), the
+    in-flight blob pair otherwise (returns the blobs); reset_source then marks the source slots with
+    BeatriceBatch_ResetStreamInFlight, which drains in neither mode.  The any-rate wrapper's state does not travel this way:
+    with_wrapper is refused."""
     if len(src_streams) != len(dst_streams):
         raise ValueError("move_streams: %d source streams, %d destination streams" % (len(src_streams), len(dst_streams)))
     if in_flight:

@@ -186,10 +186,15 @@ int BeatriceHip_ModelBlobReady(int kind, void* model);
  *       MoveStreamsInFlight work in plain tick mode -- D, H = 1 / 2 / 4, with or without the silent-block rule -- and are refused (-1; nothing changes)
  *       in A, B, C, E, F, G, P and S, where BeatriceBatch_ExportStreams / ImportStreams remain the way.  F and P keep wrapper state whose output halves
  *       run a tick or `delay` calls later: a stream at rest in the ticks is not yet at rest there.  P is served by the calls of (13), which hold that second
- *       quiescence rule; F still is not.
+ *       quiescence rule; F is served by the calls of (14), which hold its own.
  *   (13) not rows of this table either, because they are settings: BeatriceBatch_BoundStreamQuiescent, MoveBoundStreamsInFlight, ExportBoundStreamsInFlight,
  *       ImportBoundStreamsInFlight and BoundWrapperBlobBytes work exactly where the row "ProcessBlocksRaggedDevice" says ok -- P -- and are refused (-1, the
  *       size 0; nothing changes) everywhere else, D included: there the calls of (12) are the way.
+ *   (14) not rows of this table either, because they are settings: BeatriceBatch_Stream48kQuiescent, ExportStreams48kInFlight, ImportStreams48kInFlight and
+ *       MoveStreams48kInFlight work exactly where the row "ConvertBlocks48kDevice(NULL, NULL)" says ok -- F, H = 1 / 2 / 4, with or without the silent-block
+ *       rule -- and are refused (-1; nothing changes) in A, B, C, D, E, G, P and S; a move between a D batch and an F batch is refused by both families.
+ *       Their quiescence rule is that of (12) plus ONE LAUNCH: the wrapper's output half of a step runs in the wrapper launch of the call after the
+ *       step's last tick (or in the flush of a drain), and only behind it is the stream's 48 kHz wrapper state at rest.
  *
  * Environment variables the library reads: BEATRICE_HIP_DEBUG (print HIP errors to stderr), BEATRICE_HIP_CUMASK ("lo-hi;lo-hi;..": CU masks
  * of the stage-pipelining streams), BEATRICE_HIP_HOP_GRAPH (the 1-stream calls replayed as hipGraphs), BEATRICE_HIP_NO_SPECULATION (no pitch hop beside
@@ -346,12 +351,16 @@ int BeatriceBatch_ResetStream(BeatriceBatch* b, int stream);
  * activation history reads as zeros, the pitch head's previous bin is 0, all four key/value blocks of the target speaker are installed
  * at that step (BeatriceBatch_FlushSpeaker), every other per-stream setting is kept, the codebook lottery's engine is untouched.  Steps of
  * the stream already inside the pipeline finish on the old state and land in their slots unchanged.  It is not a mode entry point (no row
- * in the MODES table) and works in every mode: in plain tick mode (D: H = 1, 2, 4, with or without the silent-block rule) and in host
- * streaming (E) nothing drains and nothing synchronises -- the call launches nothing, it is host bookkeeping that applies "to the step that
- * follows" like every other setting, and a stream that sits the next step(s) out is reset at its next present step; in every other mode
- * (A, B, C, S, F, G, P) it IS BeatriceBatch_ResetStream, with whatever drain that does there.  Range checks and return codes as for
- * BeatriceBatch_ResetStream.  BeatriceBatch_Synchronize, BeatriceBatch_EnableTickPipeline(b, 0) and BeatriceBatch_StreamFlush may be
- * called while a reset is still travelling: the drain ticks carry it to the end. */
+ * in the MODES table) and works in every mode: in plain tick mode (D: H = 1, 2, 4, with or without the silent-block rule), in host
+ * streaming (E) and around the resident 48 kHz blocks (F: H = 1, 2, 4, with or without the rule) nothing drains and nothing synchronises
+ * -- the call launches nothing, it is host bookkeeping that applies "to the step that follows" like every other setting, and a stream that
+ * sits the next step(s) out is reset at its next present step; in every other mode (A, B, C, S, G, P) it IS BeatriceBatch_ResetStream,
+ * with whatever drain that does there.  In F the 48 kHz wrapper's state of the stream starts over with the model's: the blocks of the
+ * steps already inside come out behind the old wrapper state, unchanged, and the block of that step is the first block of a new stream
+ * behind a new wrapper (at H = 2 / 4 the first block of that step).  Range checks and return codes as for BeatriceBatch_ResetStream.
+ * BeatriceBatch_Synchronize, BeatriceBatch_EnableTickPipeline(b, 0), BeatriceBatch_StreamFlush, BeatriceBatch_BindResidentIO48k(NULL,
+ * NULL) and a re-bind may be called while a reset is still travelling: the drain ticks, and in F the flush of the last 48 kHz block,
+ * carry it to the end. */
 int BeatriceBatch_ResetStreamInFlight(BeatriceBatch* b, int stream);
 /* Tick launches since tick mode was entered (fill and drain ticks included); 0 outside tick mode. */
 long long BeatriceBatch_TicksLaunched(const BeatriceBatch* b);
@@ -429,6 +438,33 @@ int BeatriceBatch_ImportStreamsInFlight(BeatriceBatch* b, int n, const int* stre
                                         const int* entry_map, int n_map);
 int BeatriceBatch_MoveStreamsInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
                                       const int* entry_map, int n_map);
+
+/* The same four calls for batches that BOTH GO ON CONVERTING RESIDENT 48 kHz BLOCKS (BeatriceBatch_BindResidentIO48k, mode F).  MODES
+ * footnote (14): F, H = 1, 2 or 4, with or without the silent-block rule; refused with -1 everywhere else, D included -- and the four
+ * calls above go on refusing F, so a move between a D batch and an F batch is refused by both families.
+ * The contract is that of the calls above, word for word -- the same blobs (which already hold the 48 kHz wrapper's state of the
+ * stream), the blob's counter the stream's own, every ring turned by the destination stream's own counter minus the blob's, staging a
+ * ring of two import calls, the export waiting for its own copy alone, the move one launch per 16 streams on the destination's stream
+ * fenced by events against the source's, settings and lottery engine host to host with the entry_map checks, a pending
+ * BeatriceBatch_ResetStreamInFlight refusing a source with -3 and cancelled on a destination, the same order of refusals,
+ * BeatriceBatch_TicksLaunched and every counter unchanged -- with ONE difference: when a stream is at rest.
+ * Around the ticks of F stands the 48 kHz wrapper, and the output half of a step runs ONE LAUNCH LATE: the 48 kHz block of the step fed
+ * by call T is produced by the wrapper launch of call T + BeatriceBatch_TickStages(b), or by the flush of a drain that gets there first,
+ * and that launch reads and writes the stream's wrapper state.  BeatriceBatch_Stream48kQuiescent(b, s) is 1 when stream s has taken part
+ * in no step since the last drained point, or when that launch has been enqueued for its last present step: TickStages + 1 calls have
+ * been made since, and counting, the call that fed it -- the stream sat out for TickStages further calls, one more than in D.  From then
+ * on no launch reads or writes the stream's rings, its previous bin or its wrapper state until it is fed again: the input half of an
+ * absent stream returns early, its output half copies its own down-mix.  A BeatriceBatch_ResetStreamInFlight that is still travelling
+ * implies that the stream is not at rest.  0 otherwise; -1 for a stream out of range or outside F.
+ * The wrapper state is mono: the two bindings' channel counts and slot counts need not agree; hops per step and ring layout must, as in
+ * D.  After a move the stream's next block, written by the caller into the destination binding's next slot, comes out as the block the
+ * source would have produced -- the first one included, whose 48 kHz samples are the model output that travelled in the wrapper's FIFO. */
+int BeatriceBatch_Stream48kQuiescent(const BeatriceBatch* b, int stream);
+int BeatriceBatch_ExportStreams48kInFlight(BeatriceBatch* b, int n, const int* streams, void* blobs /* host, n * StreamBlobBytes(b) */);
+int BeatriceBatch_ImportStreams48kInFlight(BeatriceBatch* b, int n, const int* streams, const void* blobs /* host, n blobs */,
+                                           const int* entry_map, int n_map);
+int BeatriceBatch_MoveStreams48kInFlight(BeatriceBatch* src, BeatriceBatch* dst, int n, const int* src_streams, const int* dst_streams,
+                                         const int* entry_map, int n_map);
 
 /* One step (H hops, H = 1 unless created with BeatriceBatch_CreateBlock) for every stream.
  * Host variant: in [B][H*160] @16 kHz, out [B][H*240] @24 kHz, synchronous.
