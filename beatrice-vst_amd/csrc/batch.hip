@@ -531,6 +531,17 @@ void sync_stream_arrays(BeatriceBatch* b, int s) {
   b->front_dirty = true;
 }
 
+// A BeatriceBatch_ResetStreamInFlight of stream s that no step has taken yet (tick mode keeps the flags; they exist once the first
+// such call has sized them).
+bool reset_waits_for(const BeatriceBatch* b, int s) {
+  return b->tk.on && b->tk.any_reset_pending && (int)b->tk.reset_pending.size() == b->B && b->tk.reset_pending[s] != 0;
+}
+// processor_core_2.cc:270,414: `while (SetKeyValueSpeakerEmbedding());` -- every block still to come, now
+void flush_kv(StreamCfg& c) {
+  c.kv_delay = 0;
+  for (; c.kv_set_count < B_NBLOCKS; ++c.kv_set_count) c.kv_slot[c.kv_set_count] = c.target_speaker;
+}
+
 // One K/V block per stream per hop, as the reference host does before its three per-hop calls
 // (processor_core_2.cc:179-181, processor_core_2.h:161-169).
 void advance_kv(BeatriceBatch* b) {
@@ -548,6 +559,14 @@ void advance_kv(BeatriceBatch* b) {
       continue;
     }
     bool installed = false;
+    // A BeatriceBatch_ResetStreamInFlight that this step takes: the step is the first of a new stream, on all four blocks of the target the
+    // stream has NOW (the flush at the call covered the target of that moment; a switch made since, while the stream sat out or in the
+    // same gap, must not install one block per hop behind the reset).
+    if (c.kv_set_count < B_NBLOCKS && reset_waits_for(b, s)) {
+      flush_kv(c);
+      advanced = true;
+      installed = true;
+    }
     for (int hh = 0; hh < H; ++hh) {  // the hops of this step, each preceded by one block install
       if (c.kv_delay > 0) {
         --c.kv_delay;
@@ -1403,10 +1422,7 @@ int BeatriceBatch_SetTargetSpeakers(BeatriceBatch* b, int n, const int* streams,
 // processor_core_2.cc:270,414: `while (SetKeyValueSpeakerEmbedding());`
 int BeatriceBatch_FlushSpeaker(BeatriceBatch* b, int stream) {
   const DeviceScope dev_(b ? b->device : -1);
-  const int r = for_streams(b, stream, [&](StreamCfg& c) {
-    c.kv_delay = 0;
-    for (; c.kv_set_count < B_NBLOCKS; ++c.kv_set_count) c.kv_slot[c.kv_set_count] = c.target_speaker;
-  });
+  const int r = for_streams(b, stream, [&](StreamCfg& c) { flush_kv(c); });
   if (r == 0) {
     for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? b->B : stream + 1); ++s) fill_row_slots(b, s);
     b->pending_kv = 0;
@@ -1593,8 +1609,7 @@ int BeatriceBatch_ExportStreams(BeatriceBatch* b, int n, const int* streams, voi
   BATCH_OPEN(b);
   if (!blob_streams_ok(b, n, streams) || !blobs) return -1;
   // a reset that waits for the stream's next step has not happened yet: the rings still hold what it is to clear
-  if (b->tk.on && b->tk.any_reset_pending && (int)b->tk.reset_pending.size() == b->B)
-    for (int i = 0; i < n; ++i) if (b->tk.reset_pending[streams[i]]) return -3;
+  for (int i = 0; i < n; ++i) if (reset_waits_for(b, streams[i])) return -3;
   if (!blob_prepare(b, n) || !sync_all(b)) return -2;
   return export_rounds(b, n, streams, blobs, false);
 }

@@ -497,6 +497,8 @@ static bool tick_reset_settle(BeatriceBatch* b) {
     ok = b->phone.arena.zero_stream(s, b->stream) && b->pitch.arena.zero_stream(s, b->stream) && b->wave.arena.zero_stream(s, b->stream) &&
          hip_ok(hipMemsetAsync(b->pitch.d_prev_q + s, 0, sizeof(int), b->stream), "prev_q") &&
          (!b->r48.on || hip_ok(hipMemsetAsync(b->d_w48 + s, 0, sizeof(Wrap48State), b->stream), "w48 reset"));
+    // (a switch made since the call: the new stream starts on all four blocks of the target it has now, as in advance_kv)
+    if (ok && b->cfg[s].kv_set_count < B_NBLOCKS) ok = BeatriceBatch_FlushSpeaker(b, s) == 0;
   }
   std::fill(k.reset_pending.begin(), k.reset_pending.end(), 0);
   k.any_reset_pending = false;

@@ -301,8 +301,13 @@ int BeatriceBatch_MorphSpeakersInFlight(BeatriceBatch* b, int n, const int* slot
 /* 1: table entry `entry` is busy, 0: free to be a slot of BeatriceBatch_MorphSpeakersInFlight or an entry of
  * BeatriceBatch_InstallSpeakersInFlight, -1: bad argument.  Busy means (a) some
  * stream's current settings name it -- as target, additive or codebook speaker, or as an installed or pending key/value entry -- or
- * (b) in D and E, a step that named it was fed fewer than BeatriceBatch_TickStages() ticks ago and the pipeline has not been drained
- * since: that step's later stages still read the entry's additive row and key/value tables -- or (c) an active morph entry that is
+ * (b) in D and E, a step that named it may still be inside the pipeline: that step's later stages read the entry's additive row and
+ * key/value tables.  The bookkeeping is one stamp per entry and errs on the safe side: when the entry's last naming setting goes, it
+ * stays busy until BeatriceBatch_TickStages() ticks have been launched counting from the last step the BATCH had been fed at that moment
+ * (when it was a key/value install at several hops per step that took the last name away: from the step that installs, whose early hops
+ * still run on the blocks installed before), or until the pipeline is drained.  For a stream that takes part in every step that is the
+ * last step that named the entry; for a stream that changes its settings while it sits out (BeatriceBatch_SetSilentStreams), or that
+ * is imported over, it is later than that -- by the steps the batch was fed without it -- or (c) an active morph entry that is
  * itself busy by (a) or (b) lists it with positive odds (with any odds when all of the morph's weights were dropped: the lottery then
  * draws from all of its speakers): a step of a stream on that morph may have drawn the entry's codebook.  Host bookkeeping; launches
  * nothing. */
@@ -349,7 +354,8 @@ int BeatriceBatch_ResetStream(BeatriceBatch* b, int stream);
 /* The same reset as a per-stream SETTING (stream = -1: every stream): the next step fed that the stream takes part in is the first step
  * of a new stream.  The effect on that step and all later ones is exactly that of BeatriceBatch_ResetStream followed by that step: all
  * activation history reads as zeros, the pitch head's previous bin is 0, all four key/value blocks of the target speaker are installed
- * at that step (BeatriceBatch_FlushSpeaker), every other per-stream setting is kept, the codebook lottery's engine is untouched.  Steps of
+ * at that step (BeatriceBatch_FlushSpeaker; the target of THAT step: a BeatriceBatch_SetTargetSpeaker made between the call and the step
+ * does not install one block per hop behind the reset), every other per-stream setting is kept, the codebook lottery's engine is untouched.  Steps of
  * the stream already inside the pipeline finish on the old state and land in their slots unchanged.  It is not a mode entry point (no row
  * in the MODES table) and works in every mode: in plain tick mode (D: H = 1, 2, 4, with or without the silent-block rule), in host
  * streaming (E) and around the resident 48 kHz blocks (F: H = 1, 2, 4, with or without the rule) nothing drains and nothing synchronises

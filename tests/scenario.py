@@ -21,7 +21,8 @@ has sit-outs), E host streaming.  Every phase is entered from A and left to A, a
 (every mode-changing call is asserted to return 0; tests/test_cpu_scenarios.py holds `calls_of()` against csrc/batch_modes.h).  The wrapper
 modes F / G / P and S at 48 kHz are NOT covered here: their reference is the wrapper oracle, another leg: tests/wrapper_walk.py walks one batch across
 the transitions between those modes (tests/test_cpu_wrapper_walk.py, tests/test_gpu_wrapper_walk.py).  Morph slots and the codebook
-lottery are out as well (OracleBatch has no model of them).
+lottery are out as well (OracleBatch has no model of them).  The calls that change a stream's state while the ticks keep running
+(reset, install, export / import / move in flight) have a family of their own: tests/scenario_in_flight.py.
 
 Replay one scenario of the list:  python tests/scenario.py --seed N [--B .. --H .. --phases D:40,A:6] [--dump scenario.json] [--gpu]
 (without --gpu it prints the scenario and its interactions; with --gpu it runs the comparison of tests/test_gpu_scenarios.py for it)."""

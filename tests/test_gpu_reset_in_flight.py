@@ -248,6 +248,40 @@ def test_a_reset_asked_for_after_the_last_step_is_applied_when_tick_mode_is_left
     assert np.array_equal(outs["inflight"], outs["drained"])
 
 
+@pytest.mark.parametrize("H", [1, 2, 4])
+def test_a_switch_between_the_call_and_the_step_that_takes_the_reset(bv, oracle, product, model_dir, H):
+    """The reset belongs to the stream's next present step, not to the call (found by tests/scenario_in_flight.py,
+    switch_after_reset_in_flight_while_absent): stream 1 is asked to start over in the first step of its sit-out (SIT_OUT: 20..22) and
+    switched to another speaker in the second; stream 2 is asked and switched in one gap.  The step that takes the reset is
+    BeatriceBatch_ResetStream followed by that step with the settings of THAT moment -- all four key/value blocks of the new target at
+    once (at H = 4 from the step's first hop on); the switch must not go on installing one block per hop behind the reset.  The oracle makes the switch, then the reset, in front
+    of the step that takes it."""
+    B, steps = 7, 30
+
+    def asked(api, k):
+        if k == 10:
+            assert api.reset(2) == 0 and api.a.BeatriceBatch_SetTargetSpeaker(api.h, 2, 1) == 0
+        if k == 20:
+            assert api.reset(1) == 0
+        if k == 21:
+            assert api.a.BeatriceBatch_SetTargetSpeaker(api.h, 1, 2) == 0
+
+    def taken(api, k):
+        if k == 10:
+            assert api.a.BeatriceBatch_SetTargetSpeaker(api.h, 2, 1) == 0 and api.reset(2) == 0
+        if k == 21:
+            assert api.a.BeatriceBatch_SetTargetSpeaker(api.h, 1, 2) == 0
+        if k == 23:
+            assert api.reset(1) == 0
+
+    got, _, ticks = run_product(bv, product, model_dir, B, steps, H, asked, "inflight", rule=True)
+    sample, want = run_oracle(bv, oracle, model_dir, B, steps, H, taken, [0, 1, 2], rule=True)
+    assert ticks == steps and np.abs(want[:, 1]).max() > 0.05
+    absent = {s: ks for s, ks in SIT_OUT.items() if s < B}
+    bad = differing(got, want, sample, steps, absent)
+    assert not bad, "in flight vs the oracle, (stream, step, max-abs): %s" % bad[:12]
+
+
 def test_fallback_in_order_is_the_drained_reset(bv, product, model_dir):
     """Mode A: BeatriceBatch_ResetStreamInFlight is BeatriceBatch_ResetStream."""
     B, steps, H = 7, 14, 1
