@@ -291,7 +291,11 @@ namespace { constexpr int kInnerStride = wrapn::kMaxSamples + 64; }
 int BeatriceBatch_ConfigureWrapper(BeatriceBatch* b, double sample_rate) {
   BATCH_ENTER(b, Entry::ConfigureWrapper);   // (G, P: the binding restarts the wrapper itself when it is made and released; several hops per step: for BeatriceBatch_BindResidentBlocks)
   if (!sync_all(b)) return -2;
-  if (!b->wrap.configure(sample_rate)) return -1;  // rate <= 0, or a ratio whose filter history exceeds the state block
+  // rate <= 0, or a ratio whose filter history exceeds the state block: refused on a class of its own, so that the configured one -- its
+  // ratio, its tables, `ready` -- stands and the next blocks go on as if nobody had asked
+  wrapn::RateClass fresh;
+  if (!fresh.configure(sample_rate)) return -1;
+  b->wrap = std::move(fresh);
   b->wrap_clk = b->wrap.start();
   const int B = b->B;
   const size_t nt = b->wrap.taps_down.size();

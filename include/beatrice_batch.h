@@ -572,7 +572,13 @@ int BeatriceBatch_ScanBoundBlocks48k(BeatriceBatch* b, int n_calls, unsigned cha
  * (processor_core_2.cc:421-429) restarts it at a NEW rate: both resampler histories and the 480-sample FIFO become zeros, the two clocks and
  * the FIFO fill start over; both gains keep their target and their present value and ramp on, at the new rate, from the next block; model
  * state and settings are untouched.  Unlike SetSampleRate it does so at the PRESENT rate too (the reference: SetSampleRate(another rate),
- * SetSampleRate(the rate)) -- in mid-life, and after BeatriceBatch_ConfigureWrapperRates, which it replaces;
+ * SetSampleRate(the rate)) -- in mid-life, and after BeatriceBatch_ConfigureWrapperRates, which it replaces.
+ * ACCEPTED RATES: the ratio between the host rate and 48 kHz is replaced by the fraction hi/lo >= 1 of smallest denominator that the
+ * reference's search finds with both parts below 1000 (resample.h:25-46; 44.1 kHz: 160/147, 47 952 Hz: 999/998, 48 048 Hz: 1/1), and the
+ * filter history of the high-rate side, 32 hi / lo + 1 samples, must fit the per-stream state block of 257 (the division is the
+ * integer one, so what counts is hi/lo after the search: at most 8 and the sliver above it that rounds away) -- 6 kHz to 384 kHz.  A rate outside that range (5 900 Hz, 390 kHz), not finite or <= 0 is refused with -1 and NOTHING changes: the rate
+ * configured before, every stream's clocks, histories, FIFO and gains stand, and the next block goes on as if nobody had asked.  The same
+ * range holds for BeatriceBatch_ConfigureWrapperRates, BeatriceBatch_SetStreamRate and BeatriceBatch_SetStreamRateInFlight;
  * BeatriceBatch_ProcessBlocks[Device] converts one block of n samples per stream, [B][channels][n] planar, channels 1 or 2
  * (stereo is down-mixed (L+R)*0.5 as src/vst/processor.cc:183-192 does; the shell's skip of an all-zero block, :204-214,
  * is NOT applied per stream -- the streams of a batch advance together, a silent stream is converted like any other; the

@@ -17,7 +17,10 @@ import pytest
 import wrapperlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RATES = [16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000]
+import wrapper_edge_cases
+
+# ... and the rates of tests/wrapper_edge_cases.py: ratios 4, 6 and 8 on both sides of 48 kHz, tables beyond 7168 taps, truncated fractions
+RATES = [16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000] + [r for r in wrapper_edge_cases.RATES if r not in (22050.0, 48000.0)]
 _f32p = C.POINTER(C.c_float)
 
 DRIVER = r"""
@@ -209,7 +212,8 @@ def lengths_for(rate, hi):
     (>= 2 hi host samples) and that at least 30 hops fire"""
     L = longest(rate)
     rng = random.Random(1000 + rate)
-    return [1] * max(2 * hi, 600) + [97] * 40 + [480] * 12 + [L] * 6 + [rng.choice([1, 2, 7, 97, 441, 480, 512, L, rng.randint(1, L)]) for _ in range(40)]
+    n_longest = max(6, math.ceil(20 * 480 * max(1.0, rate / 48000.0) / L))   # (six up to 96 kHz; above, a block is few inner samples: 20 hops' worth)
+    return [1] * max(2 * hi, 600) + [97] * 40 + [480] * 12 + [L] * n_longest + [rng.choice([1, 2, 7, 97, 441, 480, 512, L, rng.randint(1, L)]) for _ in range(40)]
 
 
 @pytest.mark.parametrize("rate", RATES)
@@ -222,7 +226,9 @@ def test_one_stream_against_the_oracle(driver, wo, rate):
     # ends inside a call, and -- below -- a target equal to the present value, in the middle of a ramp and at rest
     events = {10: [("gain_in", -12.0)], 50: [("gain_in", 3.0)], first97: [("gain_out", -60.0)], first97 + 3: [("gain_out", 0.0)],
               first97 + 8: [("gain_in", -40.0)], first480 + 2: [("gain_out", -6.0)], first480 + 6: [("gain_in", -40.0)]}
-    present = {first97 + 10: "gain_in", first480 + 4: "gain_out"}
+    # (the 43 dB towards -40 dB take 21.5 ms: two 97-sample calls from 16 kHz up, one call -- 16 ms at 6 kHz -- below)
+    mid_ramp = first97 + (10 if rate >= 16000 else 9)
+    present = {mid_ramp: "gain_in", first480 + 4: "gain_out"}
     o = OracleStream(wo, rate)
     script, want = ["longest %r" % float(rate), "stream %r" % float(rate)], []
     for i, n in enumerate(ns):
@@ -232,7 +238,7 @@ def test_one_stream_against_the_oracle(driver, wo, rate):
         if i in present:
             g = o.state()[1]
             db = g[1] if present[i] == "gain_in" else g[3]
-            if i == first97 + 10:
+            if i == mid_ramp:
                 assert g[0] != g[1]   # (the ramp towards -40 dB is still under way)
             o.gain(present[i], db)
             script.append("%s 0 %s" % (present[i], db.hex()))

@@ -65,7 +65,7 @@ def test_device_wrapper_any_rate_with_gains(bv, oracle, product, model_dir, sr, 
     assert np.abs(want).max() > 1e-3
     if channels == 2:
         assert np.array_equal(got[:, 0], got[:, 1])
-    assert dev <= 1e-6
+    assert np.array_equal(got[:, 0], want), "max-abs %g" % dev   # (equality, not a tolerance: the same float32 mul-then-add in the same order)
 
 
 def test_device_wrapper_varying_block_sizes(bv, oracle, product, model_dir):

@@ -77,6 +77,48 @@ def test_chain_matches_reference_live(wo, ref, sr, block):
     assert np.array_equal(want, b), "max-abs %g" % np.abs(want - b).max()
 
 
+# The rates of tests/wrapper_edge_cases.py -- ratios 4, 6 and 8 on both sides of 48 kHz, tap tables beyond 7168 floats, fractions the < 1000
+# search truncates -- with the table's own scripts: steady 10 ms blocks around 48 calls of one sample everywhere, and MaxWrapperBlock three
+# times in a row where the table takes it (three calls at 384 kHz too: the recording stays small).  Both gains ramp in both directions.
+EDGE_GAINS = {1: (-24.0, 6.0), 2: (3.0, -18.0), 20: (-9.0, 2.0)}
+
+
+def edge_cases():
+    import wrapper_edge_cases as E
+    cases = [(rate, "ones", E.script_blocks(rate, "ones")) for rate in E.RATES if rate != 48000.0]
+    cases += [(rate, "longest", E.script_blocks(rate, "longest")[:3]) for rate in (6000.0, 11025.0, 384000.0)]
+    return cases
+
+
+def edge_input(rate, kind, blocks):
+    return wrapperlib.test_signal(sum(blocks), int(rate), seed=3000 + int(rate) % 977 + (500 if kind == "longest" else 0))
+
+
+@pytest.mark.parametrize("rate,kind,blocks", edge_cases(), ids=lambda v: None if isinstance(v, list) else str(v))
+def test_edge_rate_chain_matches_reference_live(wo, ref, rate, kind, blocks):
+    """as test_chain_matches_reference_live, at the table's rates: live where oracle/_ref is built, and always against the reference's outputs
+    as recorded in reference_cases_edge_rates.npz (tools/make_golden.py edge_rates).  Outputs only; the inputs come from seeds."""
+    x = edge_input(rate, kind, blocks)
+    want = np.load(os.path.join(GOLD, "reference_cases_edge_rates.npz"))["chain_%s_%s" % (repr(rate), kind)]
+    if ref is not None:
+        a = ref.run_blocks(rate, x, blocks, gains=EDGE_GAINS)
+        assert np.array_equal(a, want), "recording out of date: max-abs %g" % np.abs(a - want).max()
+    b = wo.run_blocks(rate, x, blocks, gains=EDGE_GAINS)
+    assert np.array_equal(want, b), "max-abs %g, first at %d" % (np.abs(want - b).max(), int(np.argmax(want != b)))
+    assert np.isfinite(want).all() and np.abs(want[int(0.03 * rate):]).max() > 1e-3
+
+
+def test_edge_rate_fractions_match_the_reference(wo, ref):
+    """the table's fractions (and the four rates the product refuses) through the oracle's search and, where built, the reference's"""
+    import wrapper_edge_cases as E
+    for rate, frac in list(E.RATES.items()) + [(r, None) for r in E.REFUSED_RATES]:
+        ratio = max(rate, 48000.0) / min(rate, 48000.0)
+        got = wo.fraction(ratio)
+        assert got == E.simple_fraction(ratio) and (frac is None or got == frac), (rate, got, frac)
+        if ref is not None:
+            assert ref.fraction(ratio) == got, rate
+
+
 VANISHING_CASES = [(44100, 441), (48000, 480), (16000, 333)]
 
 

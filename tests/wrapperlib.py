@@ -79,6 +79,28 @@ class Wrapper:
         self.f_destroy(p)
         return out
 
+    def run_blocks(self, sample_rate, x, blocks, hop=stub_hop, gains=None, rate_at=None):
+        """Stream x through Process() in calls of blocks[k] samples.  gains: call -> (input dB or None, output dB or None), set in front
+        of that call; rate_at: call -> host rate, SetSampleRate in front of that call (before the gains)."""
+        cb = HOP_FN(hop)
+        p = self.f_create(float(sample_rate), cb, None)
+        x = np.ascontiguousarray(x, np.float32)
+        assert len(x) == sum(blocks)
+        out = np.zeros_like(x)
+        pos = 0
+        for k, n in enumerate(blocks):
+            if rate_at and k in rate_at:
+                self.f_set_rate(p, float(rate_at[k]))
+            gin, gout = (gains or {}).get(k, (None, None))
+            if gin is not None:
+                self.f_in_gain(p, gin)
+            if gout is not None:
+                self.f_out_gain(p, gout)
+            assert self.f_process(p, x[pos:pos + n].ctypes.data_as(_f32p), out[pos:pos + n].ctypes.data_as(_f32p), n) == 0
+            pos += n
+        self.f_destroy(p)
+        return out
+
     def gain_state(self, p):
         """(input target, input now, output target, output now) in dB"""
         v = [C.c_double(0.0) for _ in range(4)]

@@ -144,8 +144,27 @@ def rate_walk():
     print("wrapper_rate_walk.npz %d bytes" % os.path.getsize(os.path.join(GOLD, "wrapper_rate_walk.npz")))
 
 
+def edge_rates():
+    """reference_cases_edge_rates.npz: the reference library's results for tests/test_wrapper_oracle.py::test_edge_rate_chain_matches_reference_live
+    -- the rates and block scripts of tests/wrapper_edge_cases.py.  Outputs only: the inputs come from seeds.
+    Run where the reference exists:  make -C oracle && python tools/make_golden.py edge_rates"""
+    ref = wrapperlib.ref_wrapper()
+    if ref is None:
+        raise SystemExit("oracle/_ref/libref_wrapper.so missing: run `make -C oracle` where the reference exists")
+    import test_wrapper_oracle as t
+    g = {}
+    for rate, kind, blocks in t.edge_cases():
+        g["chain_%s_%s" % (repr(rate), kind)] = ref.run_blocks(rate, t.edge_input(rate, kind, blocks), blocks, gains=t.EDGE_GAINS)
+    path = os.path.join(GOLD, "reference_cases_edge_rates.npz")
+    np.savez_compressed(path, **g)
+    print("reference_cases_edge_rates.npz %d bytes, %d arrays (reference_cases.npz: %d bytes)" % (
+        os.path.getsize(path), len(g), os.path.getsize(os.path.join(GOLD, "reference_cases.npz"))))
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["reference_cases"]:
+    if sys.argv[1:] == ["edge_rates"]:
+        edge_rates()
+    elif sys.argv[1:] == ["reference_cases"]:
         reference_cases()
     elif sys.argv[1:] == ["rate_walk"]:
         rate_walk()
