@@ -88,7 +88,7 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   // publishes into link t, the last hop only polls.  A cell must find its predecessor's states published when it starts (it holds a
   // slot while it waits), so the hops sit far apart in dispatch order: hop 0 ahead of every other body, the later ones at the points
   // marked gru_at() below, each behind at least one more round of the launch's workgroups.
-  // (GruArgs::passes, the column-split cells only -- both cells at one hop per step, hop 0 of the phone GRU at four: two row groups per workgroup from 512
+  // (GruArgs::passes, the column-split cells only -- both cells at one hop per step: two row groups per workgroup from 512
   //  streams on; BEATRICE_HIP_GRU_PASSES overrides, for measurements.  The rows cells stream their weights and ignore it)
   // time of a rows cell's workgroup (us; the means of a full four-hop tick's timeline at 256 streams, profiles/gru_rows_notes.md
   // section 6: phone 23.8 / 25.9, pitch 11.0 / 20.0 / 15.8 by hop): what two_halves balances on
@@ -97,9 +97,17 @@ bool tick_build_table_h(BeatriceBatch* b, const bool sparse) {
   constexpr double kGruRowsCostP = 25, kGruRowsCostQ = H == 2 ? 14 : 17;
   static const int gru_passes_env = bhip::meas_env("BEATRICE_HIP_GRU_PASSES") ? std::atoi(bhip::meas_env("BEATRICE_HIP_GRU_PASSES")) : 0;
   const int gru_passes = gru_passes_env > 0 ? gru_passes_env : (B >= 512 ? 2 : 1);
-  // (hop 0: the column-split cells at one hop per step, 19 / 12 us; the phone cell of hop 0 at four hops is that cell too, tick.hip.h GruP)
+  // (hop 0: the column-split cells at one hop per step, 19 / 12 us; at two and four hops every cell is the rows cell, tick.hip.h GruP / GruQ.
+  //  The hop-0 phone cell at FOUR hops: its workgroups last 16 us (hop 0 polls nothing), but the figure is the WEIGHT of the phone cells'
+  //  half of the chip in two_halves, and where the other pinned bodies land moves the launch by more than the cell is worth -- 256 x 4
+  //  with 12 / 25 / 38 / 50 / 76: 200.7 / 206.7 / 201.4 / 201.7 / 200.4 us against the parent's 203.4.  76 = 19 x 128 / 32 is the
+  //  column-split cell's total over the rows cell's 32 workgroups (38 from 512 streams on, where that cell walked two row groups per
+  //  workgroup and weighed half as much per stream): every other body stays on the half that the order had it on with the column-split
+  //  cell; profiles/tail_substeps_notes.md section 4.  BEATRICE_HIP_GRU_COST0, measurement builds: that scan's knob)
+  const double gru_cost0_p = H == 1 ? 19 : (H == 2 ? kGruRowsCostP : (B >= 512 ? 38 : 76));
+  static const double gru_cost0_env = bhip::meas_env("BEATRICE_HIP_GRU_COST0") ? std::atof(bhip::meas_env("BEATRICE_HIP_GRU_COST0")) : 0.0;
   const TickGruCell<T_PGRU, T_PGRUM, T_PGRU1> pgru{ps.rb[3], ps.h, pw.gru_wih, pw.gru_whh, pw.gru_bih, pw.gru_bhh, k.d_link_p, 256, Plan::PGRU,
-                                                  H == 2 ? kGruRowsCostP : 19, kGruRowsCostP, k.h_link_dead, gru_passes};
+                                                  gru_cost0_env > 0 ? gru_cost0_env : gru_cost0_p, kGruRowsCostP, k.h_link_dead, gru_passes};
   const TickGruCell<T_QGRU, T_QGRUM, T_QGRU1> qgru{qs.p[2], qs.h, qw.gru_wih, qw.gru_whh, qw.gru_bih, qw.gru_bhh, k.d_link_q, 128, Plan::QGRU,
                                                   H == 1 ? 12 : kGruRowsCostQ, kGruRowsCostQ, k.h_link_dead, gru_passes};
   auto add_pgru = [&](int t) { pgru.add(tt, B, t); };

@@ -41,11 +41,15 @@
 #include "spec_math.hip.h"
 #include "wave_tail.hip.h"
 
-// tools/microbench/tst_timing.hip: shader-clock stamps of wavefront 0 at the phase boundaries of a stage body
+// tools/microbench/tst_timing.hip: shader-clock stamps of wavefront 0 at the phase boundaries of a stage body.  A body that runs its
+// step as sub-steps stamps sub-step u at [10 u, 10 u + 8] (TST_SUB; 8 = behind the sub-step boundary, or the end of the body)
 #ifdef TST_TIMING
-__device__ unsigned long long* g_tst_stamps;   // [workgroups][16]
-#define TST_STAMP(i) do { if (threadIdx.x == 0) g_tst_stamps[(size_t)blockIdx.x * 16 + (i)] = __builtin_readcyclecounter(); } while (0)
+__device__ unsigned long long* g_tst_stamps;   // [workgroups][32]
+__shared__ int g_tst_sub;                      // (thread 0's alone)
+#define TST_SUB(u) do { if (threadIdx.x == 0) g_tst_sub = 10 * (u); } while (0)
+#define TST_STAMP(i) do { if (threadIdx.x == 0) g_tst_stamps[(size_t)blockIdx.x * 32 + g_tst_sub + (i)] = __builtin_readcyclecounter(); } while (0)
 #else
+#define TST_SUB(u) do { } while (0)
 #define TST_STAMP(i) do { } while (0)
 #endif
 
@@ -496,6 +500,11 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const 
   float* HC = HIN + S * 2 * C;              // [S][1][C] activated
   const int hop = stepc::step(a.hop);
   if (hop < 0) return;
+  // (the output ring's common position once, as a scalar: the division behind `hop % m` runs on the vector pipe, and worked out where the
+  //  transposed conv's epilogue needs it, its operand |hop| stayed in a vector register across all three layers -- in T1, where registers
+  //  are shortest, as a spill stored at the top of the body and reloaded behind the last layer's MFMAs; rowchain.hip.h gru_rows_body)
+  const int pos_o = __builtin_amdgcn_readfirstlane(ring_pos(a.out, hop));
+  asm volatile("" : : "s"(pos_o));
   const int b0 = g * S;
   const int n_rows = (a.B - b0 < S ? a.B - b0 : S) * T;
   int* shop = reinterpret_cast<int*>(lds + stage_lds<C, T, S, 1>() - 8);
@@ -508,6 +517,7 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const 
     if constexpr (NSUB > 1) asm volatile("" : "+v"(tid));
     const int lane = tid & 63, wave = tid >> 6;
     float4 bfa[Split<C>::CT][3 * C / 16], bfb[Split<C>::CT][3 * C / 16], bfu[Split<NUP>::CT][2 * C / 16];
+    TST_SUB(fb / T);
     TST_STAMP(0);
     fetch_b<3 * C, C>(a.w[0], bfa, wave, lane);
     if (first) stream_hops<S, RAG>(a, hop, b0, shop);
@@ -530,7 +540,6 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const 
       float bias_u[SU::CT];
 #pragma unroll
       for (int ct = 0; ct < SU::CT; ++ct) bias_u[ct] = TBase::of(a.b[2]).ldf((unsigned)((SU::POW2 ? wave % SU::NWN : ct) * 16 + (lane & 15)) * 4u);
-      const int pos_o = ring_pos(a.out, hop);
       const TBase gout = ring_wg(a.out, b0);
       float none[n_pass<NUP, T, S>()][2][SU::CT][4];   // (no residual in this layer: never read, costs no registers)
       layer<C, NUP, 2, 1, T, S, 0>(X, bfu, n_rows, wave, lane, none, [](int, int, int, int, float (&)[4]) {},
@@ -548,6 +557,7 @@ __device__ __forceinline__ void res_res_up_body(const StageArgs& a_table, const 
         __syncthreads();
         carry_histories<C, T, S, 1>(X, Y, HC, tid);
         __syncthreads();
+        TST_STAMP(8);
       }
     }
   };
@@ -646,9 +656,13 @@ __device__ __forceinline__ void t3_body(const StageArgs& a_table, const int g, f
   for (int sub = 0; sub < NSUB; ++sub) {
     const int fb = NSUB > 1 ? sub * T : 0;
     const bool first = NSUB == 1 || sub == 0, last = NSUB == 1 || sub == NSUB - 1;
+    TST_SUB(sub);
+    TST_STAMP(0);
     prologue<C, T, S, TS_YA4, TS_YB4, TS_YC4, 6, false, RAG>(a, hop, b0, X, Y, HIN, HC, tid, shop, fb, first, last);
     if (first && tid < 7 * 16) FW[tid] = fw;
+    TST_STAMP(1);
     __syncthreads();
+    TST_STAMP(2);
     two_res_layers<C, T, S, TS_YB4, TS_YC4, 6, RAG>(a, hop, b0, n_rows, X, Y, HC, bfa, bfb, wave, lane, tid, [] {}, [] {}, shop, nullptr, fb, last);
     // ---- output conv over the ACTIVATED frames: one thread per sample, the multiply-adds of wave_tail.hip.h in the same order
     if (tid < S * T) {
@@ -663,15 +677,18 @@ __device__ __forceinline__ void t3_body(const StageArgs& a_table, const int g, f
         gd.stf((unsigned)(s * (T * NSUB) + fb + t) * 4u, 0, bsp::tanh2(bsp::splat2(acc + fin_b)).x);   // (the packed form is the shorter one even for a single value)
       }
     }
+    TST_STAMP(7);
     if constexpr (NSUB > 1) {
       if (!last) {
         __syncthreads();
         carry_histories<C, T, S, 6>(X, Y, HC, tid);
         __syncthreads();
+        TST_STAMP(8);
       }
     }
   }
   hin_to_state<C, S, TS_YA4, RAG>(a, HIN, b0, tid, shop);
+  TST_STAMP(8);
 }
 template <int S = kT3Streams, int HOPS = 1, int NSUB = 1>
 struct T3OpS {

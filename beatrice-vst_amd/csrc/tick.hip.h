@@ -176,10 +176,10 @@ struct Ops {
   // (one hop per step: both cells stay column-split -- there the cells sit at the END of the dispatch order, and 16-32 workgroups of
   //  17-25 us end the launch later than 64-128 of 9-12 us: 61.8 -> 68.9 us per tick at 256 streams, profiles/gru_rows_notes.md section 5)
   using GruQ = std::conditional_t<H == 1, GruOp<128, 128, 2, 0>, rc::GruRowsOp<128, 128, 1>>;
-  // (the phone cell of HOP 0 at four hops per step stays the column-split cell, fused_small.hip.h: with the rows cell in this place of
-  //  the type list the common four-hop kernel comes out at 18 VGPR spills -- one more, in the tail's T1 -- and that kernel is pinned
-  //  to 17, tests/test_cpu_tick_kernel_resources.py; profiles/gru_rows_notes.md)
-  using GruP = std::conditional_t<H == 2, rc::GruRowsOp<256, 256, 1>, GruOp<256, 256, 2, (H > 1 ? 1 : 0)>>;
+  // (the phone cell of hop 0 at four hops per step is the rows cell as well: the one VGPR spill it used to bring to the common four-hop
+  //  kernel sat in the tail's T1 -- the operand of its output ring's `hop % m` -- and T1 now keeps that position as a scalar,
+  //  tail_stages.hip.h res_res_up_body; profiles/tail_substeps_notes.md)
+  using GruP = std::conditional_t<H == 1, GruOp<256, 256, 2, 0>, rc::GruRowsOp<256, 256, 1>>;
   using GruQ1 = std::conditional_t<H == 1, rc::NopOp, rc::GruRowsOp<128, 128, 2>>;
   using GruP1 = std::conditional_t<H == 1, rc::NopOp, rc::GruRowsOp<256, 256, 2>>;
   using GruQm = std::conditional_t<H <= 2, rc::NopOp, rc::GruRowsOp<128, 128, 3>>;

@@ -1,7 +1,7 @@
 """Summarise a BEATRICE_HIP_TICK_TRACE dump: per body type, workgroup count and duration; makespan; slot utilisation."""
 import sys
 import numpy as np
-NAMES = "f1 fft f2 f3 f4 f5 p1 rb p23 pout head out cond inp up1 res1a res1b up2 qgru pgru vq tail tail1 tail2 tail3 blkA1 blkA2 blkA4 blkA8 blkB blkBq f4s f5s rbs p1s up1s tail1s tail2s qgru1 pgru1 qgrum pgrum f2l f3l p23l poutl outl inpl up1l res1al res1bl up2l".split()
+NAMES = "f1 fft f2 f3 f4 f5 p1 rb p23 pout head out cond inp up1 res1a res1b up2 qgru pgru vq tail1 tail2 tail3 blkA1 blkA2 blkA4 blkA8 blkB blkBq f4s f5s rbs p1s up1s tail1s tail2s qgru1 pgru1 qgrum pgrum f2l f3l p23l poutl outl inpl up1l res1al res1bl up2l".split()
 d = np.loadtxt(sys.argv[1], dtype=np.uint64).astype(np.int64)
 d = d[d[:, 1] > 0]
 d = d[np.abs(d[:, 0] - np.median(d[:, 0])) < 100000]   # (entries of workgroups that left at once keep an older tick's stamps: beyond 1 ms of the median start)
@@ -16,7 +16,7 @@ print("workgroups %d, makespan %.1f us, sum of workgroup time %.0f us -> %.1f wo
 for t in sorted(set(typ.tolist())):
     m = typ == t
     name = NAMES[t] if 0 <= t < len(NAMES) else "idle"
-    print("  %-6s n %4d  dur mean %6.1f max %6.1f  first start %6.1f  last end %6.1f" % (name, m.sum(), (end - start)[m].mean(), (end - start)[m].max(), start[m].min(), end[m].max()))
+    print("  %-6s n %4d  dur mean %6.1f max %6.1f  slot-us %7.0f  first start %6.1f  last end %6.1f" % (name, m.sum(), (end - start)[m].mean(), (end - start)[m].max(), (end - start)[m].sum(), start[m].min(), end[m].max()))
 # residency over time: workgroups resident per 5 us bin, split heavy (mean duration >= 25 us) / other
 dur = end - start
 heavy_types = {t for t in set(typ.tolist()) if dur[typ == t].mean() >= 25.0}

@@ -19,7 +19,7 @@ __global__ __launch_bounds__(512, 4) void body_kernel(const typename Op::Args a)
 EACH(OpF2); EACH(OpF3); EACH(OpF4); EACH(OpF5); EACH(OpRB); EACH(OpOUT); EACH(OpP1); EACH(OpP23); EACH(OpPOUT); EACH(OpINP);
 EACH(OpUP1); EACH(OpRES1A); EACH(OpRES1B); EACH(OpUP2); EACH(T1); EACH(T2); EACH(T3); EACH(GruQ); EACH(GruP); EACH(Vq);
 INST(2, GruQ1); INST(2, GruP1); INST(4, GruQ1); INST(4, GruP1); INST(4, GruQm); INST(4, GruPm);   // the linked cells: last hop; middle hops
-// the rows cell of the tick tables at the phone GRU's size in every link form (the hop-0 phone cell of the four-hop table is the column-split cell: tick.hip.h),
+// the rows cell of the tick tables at the phone GRU's size in every link form (EACH(GruP) above holds its hop-0 form at two and four hops),
 // and its other split, 16 streams x 128 hidden units
 template __global__ void body_kernel<rc::GruRowsOp<256, 256, 1>, 0>(const GruArgs);
 template __global__ void body_kernel<rc::GruRowsOp<256, 256, 0, 1>, 0>(const GruArgs); template __global__ void body_kernel<rc::GruRowsOp<128, 128, 0, 1>, 0>(const GruArgs);

@@ -1,5 +1,5 @@
-// The tail stages' T1 and T2 bodies at four hops per step (tail_stages.hip.h, the shapes of the tick launch: one stream per workgroup,
-// T2 in two sub-steps) as launches of their own, with the argument block READ FROM A TABLE IN DEVICE MEMORY as in the tick launch --
+// The tail stages' T1, T2 and T3 bodies at four hops per step (tail_stages.hip.h, the shapes of the tick launch: one stream per workgroup,
+// T2 and T3 in two sub-steps) as launches of their own, with the argument block READ FROM A TABLE IN DEVICE MEMORY as in the tick launch --
 // its pointers are then generic to the compiler, and -DTST_GLOBAL=0 compiles to flat loads and stores as the tick's bodies did.
 // Built twice (tools/README.md): tail_stage_loop_flat with -DTST_GLOBAL=0, tail_stage_loop_global without; run one after the other,
 // they print the same checksums at copies = 1 (compare the two outputs with `diff` after cutting the timing fields, tools/README.md).
@@ -85,5 +85,11 @@ int main(int argc, char** argv) {
   float* ring_mid2 = device_floats(n_mid, 2, 0.5f);   // (T2's input as it was before T1 ran: the two bodies are timed apart)
   a.state = state2; a.in = Ring{ring_mid2, 32, 80 * H, 2}; a.out = Ring{ring_out, 16, 240 * H, 2};
   run<tst::T2OpS<1, H, 2>>("T2 (1 stream, 2 x 160 frames)", a, copies, ring_out, n_out, state2, n_state);
+  float* ring_out2 = device_floats(n_out, 3, 0.5f);   // (T3's input as it was before T2 ran)
+  float* state3 = device_floats(n_state, 4, 0.5f);
+  const size_t n_samples = (size_t)B * 240 * H;
+  float* samples; CHECK(hipMalloc(&samples, n_samples * 4)); CHECK(hipMemset(samples, 0, n_samples * 4));
+  a.state = state3; a.in = Ring{ring_out2, 16, 240 * H, 2}; a.out = Ring{}; a.d_out = samples; a.io_stride = 0;
+  run<tst::T3OpS<1, H, 2>>("T3 (1 stream, 2 x 480 frames)", a, copies, samples, n_samples, state3, n_state);
   return 0;
 }

@@ -9,7 +9,10 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES; do
   rm -rf "$OUT/pmc_$C"
-  rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o pmc -- python "$ROOT/bench.py" --full --no-extras --steps 200 --warmup 5 > /dev/null 2>&1
+  # (each pass a run of its own under its own time limit; nothing more is started once one has failed)
+  timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o pmc -- python "$ROOT/bench.py" --full --no-extras --steps 200 --warmup 5 > /dev/null 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then echo "counter pass failed (exit $rc): $C"; exit $rc; fi
   CSV=$(find "$OUT/pmc_$C" -name 'pmc_counter_collection.csv' | head -1)
   mkdir -p "$OUT/pmc_r1_$C"
   [ -n "$CSV" ] && cp "$CSV" "$OUT/pmc_r1_$C/pmc_counter_collection.csv"
