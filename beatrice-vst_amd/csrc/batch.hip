@@ -26,6 +26,7 @@
 #include "bound_move_plan.h"
 #include "beatrice_batch.h"
 #include "silent_scan_plan.h"
+#include "speaker_entry_plan.h"
 #include "stream_blob.h"
 #include "stream_move_plan.h"
 #include "tick.hip.h"
@@ -125,14 +126,11 @@ struct BeatriceBatch {
   std::vector<StreamCfg> cfg;
   std::vector<MorphSlot> morph;  // [max_speakers]
   int n_morph_slots = 0;
-  // Which table entries the streams' settings name, kept by COUNT so that no step has to look at every stream (entry_busy;
-  // BeatriceBatch_SpeakerEntryBusy): entry_named[s] is what recount() last counted for stream s -- target, additive and codebook
-  // speaker, the four installed key/value entries (a pending install names the target).  entry_free_at: tick mode, the first tick by
-  // which no step inside the pipeline names the entry any more, stamped when its last reference goes.
+  // Which table entries the streams' settings name and which a step may still read (entry_busy; BeatriceBatch_SpeakerEntryBusy): the
+  // counts, the stamps and their rule are speaker_entry_plan.h's.  A stream names kNamed entries -- target, additive and codebook
+  // speaker, the four installed key/value entries (a pending install names the target).
   static constexpr int kNamed = 3 + B_NBLOCKS;
-  std::vector<int> entry_refs;            // [max_speakers]
-  std::vector<long long> entry_free_at;   // [max_speakers]
-  std::vector<int> entry_named;           // [B][kNamed]
+  sentry::Plan entries;
   // BeatriceBatch_MorphSpeakersInFlight: a call's descriptors, read by its kernels in place (the host runs ahead of the device)
   static constexpr int kMorphStaging = 8;
   StagedRing<MorphDesc> morph_descs;      // [kMorphStaging][max_speakers]
@@ -334,6 +332,7 @@ struct BeatriceBatch {
     long long hops_done = 0;                                 // hops of the steps fed by the end of the previous call
     int H = 1;                                               // hops per step of the batch
     long long hops_fed() const { return hops_fired / H * H; }   // ... of which the hops of full steps are inside (or through) the ticks
+    bool step_open = false;                                  // a hop has fired into a step that is not fed yet, or is being fed (speaker_entry_plan.h)
     struct Job {
       long long call, t0; wrapn::Dir dout;
       long long last_hop() const { return (t0 + dout.n_in - 1) / wrapn::kBlock - 1; }   // the newest model hop its samples come from (wrap_post_kernel)
@@ -503,16 +502,15 @@ void fill_row_slots(BeatriceBatch* b, int s) {
 // Brings the entry reference counts up to stream s's settings.  An entry whose last reference goes is still read by the steps inside the
 // tick pipeline that were fed while it was named: the last of them is the step fed last -- or the one about to be fed
 // (next_step_too: advance_kv at several hops per step, whose early hops still run on the blocks installed before).
+// What the stamp reads of the pipeline (speaker_entry_plan.h): the tick counters, and whether a step of the uniform any-rate blocks is
+// still filling.
+sentry::Clock entry_clock(const BeatriceBatch* b) {
+  return {b->tk.tick, b->tk.last_feed_tick, b->tk.plan.count(), b->rb.on && b->rb.step_open};
+}
 void recount(BeatriceBatch* b, int s, bool next_step_too = false) {
   const StreamCfg& c = b->cfg[s];
   const int now[BeatriceBatch::kNamed] = {c.target_speaker, c.additive_speaker, c.codebook_speaker, c.kv_slot[0], c.kv_slot[1], c.kv_slot[2], c.kv_slot[3]};
-  int* seen = &b->entry_named[(size_t)s * BeatriceBatch::kNamed];
-  for (int i = 0; i < BeatriceBatch::kNamed; ++i) {
-    if (seen[i] == now[i]) continue;
-    ++b->entry_refs[now[i]];
-    if (--b->entry_refs[seen[i]] == 0) b->entry_free_at[seen[i]] = (next_step_too ? b->tk.tick : b->tk.last_feed_tick) + b->tk.plan.count();
-    seen[i] = now[i];
-  }
+  b->entries.name(s, now, entry_clock(b), next_step_too);
 }
 
 void sync_stream_arrays(BeatriceBatch* b, int s) {
@@ -788,13 +786,9 @@ using modes::Entry;
 modes::Flags flags_of(const BeatriceBatch* b) {
   return {b->tk.on, b->hs.on, b->r48.on, b->rb.on, b->rb.ragged, b->silent.on, b->pipelined, b->io_slots > 0, b->H, b->wrap.ready, b->rw.ready};
 }
-// (a) some stream's settings name the entry; (b) plain tick mode and host streaming: a step that named it is still inside the pipeline
-// (a drain runs the ticks that bring tk.tick up to every stamp)
-bool entry_named(const BeatriceBatch* b, int e) {
-  if (b->entry_refs[e] > 0) return true;
-  const modes::Mode mode = modes::mode_of(flags_of(b));
-  return (mode == modes::Mode::D || mode == modes::Mode::E) && b->tk.tick < b->entry_free_at[e];
-}
+// (a) some stream's settings name the entry; (b) in tick mode and every mode around it (D, E, F, G, P): a step that named it is still
+// inside the pipeline, or still filling (speaker_entry_plan.h; a drain runs the ticks that bring tk.tick up to every stamp)
+bool entry_named(const BeatriceBatch* b, int e) { return b->entries.busy(e, b->tk.tick, modes::mode_of(flags_of(b))); }
 // ... or (c) its CODEBOOK may be what a step drew: recount() counts the codebook of a stream's last hop, not the lottery's candidates
 // (draw_codebooks), so an entry is also busy while an active morph entry m that is itself named -- (a) or (b): the steps that could have
 // drawn from m's list are exactly the steps that named m -- lists it with positive odds, or with any odds when all of m's are zero (the
@@ -965,8 +959,7 @@ BeatriceBatch* BeatriceBatch_CreateBlock(const Beatrice20rc0_PhoneExtractor* pho
        b->d_add_raw.alloc((size_t)S * B_HID, "add") && b->d_frm_raw.alloc((size_t)9 * B_HID, "frm") && b->d_kv_raw.alloc(kvf, "kv");
   b->cfg.assign(B, StreamCfg());
   b->morph.assign(S, MorphSlot());
-  b->entry_refs.assign(S, 0); b->entry_free_at.assign(S, 0); b->entry_named.assign((size_t)B * BeatriceBatch::kNamed, 0);
-  b->entry_refs[0] = B * BeatriceBatch::kNamed;   // (StreamCfg's defaults: every stream on entry 0)
+  b->entries.start(B, S, BeatriceBatch::kNamed);   // (StreamCfg's defaults: every stream on entry 0)
   b->lottery.resize(B);
   for (int s = 0; s < B; ++s) b->lottery[s].seed(5489u + (unsigned)s);
   {  // layout of the settings block (256-byte aligned arrays)
@@ -1243,9 +1236,10 @@ int BeatriceBatch_MorphSpeakerStaged(BeatriceBatch* b, int slot, int from_slot, 
   for (const StreamCfg& c : b->cfg) if (c.kv_set_count < B_NBLOCKS) ++b->pending_kv;
   return 0;
 }
-// Many entries in one call, and in plain tick mode and host streaming WITHOUT the drain (beatrice_batch.h): the entries are refused
-// while anything still reads them (entry_busy), so their tables may be rewritten between two ticks -- two launches on the batch's stream
-// in front of the next tick (morph.hip: all solves, all projections), the descriptors in a pinned ring because the host runs ahead.
+// Many entries in one call, and in tick mode and every mode around it (D, E, F, G, P) WITHOUT the drain (beatrice_batch.h): the entries
+// are refused while anything still reads them (entry_busy), so their tables may be rewritten between two ticks -- two launches on the
+// batch's stream in front of the next tick (morph.hip: all solves, all projections), the descriptors in a pinned ring because the host
+// runs ahead.  The wrapper launches of F, G and P ride on the same stream and read no speaker table.
 int BeatriceBatch_MorphSpeakersInFlight(BeatriceBatch* b, int n, const int* slots, const int* from_slots, const float* weights, int n_weights,
                                         unsigned seed) {
   BATCH_OPEN(b);
@@ -1263,8 +1257,7 @@ int BeatriceBatch_MorphSpeakersInFlight(BeatriceBatch* b, int n, const int* slot
     is_from[f] = 1;
   }
   for (int i = 0; i < n; ++i) if (entry_busy(b, slots[i])) return -3;
-  const modes::Mode mode = modes::mode_of(flags_of(b));
-  const bool in_flight = mode == modes::Mode::D || mode == modes::Mode::E;
+  const bool in_flight = sentry::rule_b_applies(modes::mode_of(flags_of(b)));   // (D, E, F, G, P: entry_busy has asked rule (b))
   if (!b->morph_descs.entries() && !b->morph_descs.alloc(BeatriceBatch::kMorphStaging, (size_t)S, "morph descriptors")) return -2;
   if (!in_flight && !sync_all(b)) return -2;
   const int ring = (int)(b->morph_calls % BeatriceBatch::kMorphStaging);
@@ -1308,7 +1301,7 @@ int BeatriceBatch_SpeakerEntryBusy(const BeatriceBatch* b, int entry) {
   if (!b || !b->ok || entry < 0 || entry >= b->max_speakers) return -1;
   return entry_busy(b, entry) ? 1 : 0;
 }
-// BeatriceBatch_UpdateSpeaker for n entries in one call, and in plain tick mode and host streaming without the drain, on the same terms
+// BeatriceBatch_UpdateSpeaker for n entries in one call, and in D, E, F, G and P without the drain, on the same terms
 // as the morph call above: entries nothing reads (entry_busy) are rewritten between two ticks by two launches on the batch's stream.  The
 // caller's tables are copied into a pinned ring entry here, on the calling thread; install_entries_kernel (install.hip) reads them in
 // place and writes the raw tables, the transposed codebooks and their norms, morph_project_kernel (morph.hip) projects the rest.
@@ -1324,8 +1317,7 @@ int BeatriceBatch_InstallSpeakersInFlight(BeatriceBatch* b, int n, const int* en
     is_entry[entries[i]] = 1;
   }
   for (int i = 0; i < n; ++i) if (entry_busy(b, entries[i])) return -3;
-  const modes::Mode mode = modes::mode_of(flags_of(b));
-  const bool in_flight = mode == modes::Mode::D || mode == modes::Mode::E;
+  const bool in_flight = sentry::rule_b_applies(modes::mode_of(flags_of(b)));   // (D, E, F, G, P: entry_busy has asked rule (b))
   if (!b->install_tables.entries()) {
     StagedRing<float> tables;
     PinnedBuf<MorphDesc> descs;

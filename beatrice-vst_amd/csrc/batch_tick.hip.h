@@ -697,6 +697,7 @@ bool tick_run(BeatriceBatch* b, bool feeding) {
     b->steps_enqueued += 1;
     k.n_fed += 1;
     k.last_feed_tick = k.tick;
+    b->entries.fed(k.tick, k.plan.count());   // (speaker_entry_plan.h: entries that waited for a filling step get their stamp)
   }
   prof.lap(4);
   k.tick += 1;
@@ -851,7 +852,7 @@ int tick_enable(BeatriceBatch* b, bool on) {
     }
     if (!hip_ok(hipDeviceSynchronize(), "tick sync")) return -2;
     k.tick = 0; k.n_fed = 0; k.last_feed_tick = -1000; k.snap_cur = -1; k.snap_next = 0;
-    std::fill(b->entry_free_at.begin(), b->entry_free_at.end(), 0);   // (stamps of an earlier stay in tick mode: the pipeline is empty)
+    b->entries.clear_at_drained_point();   // (stamps of an earlier stay in tick mode: the pipeline is empty)
     k.resets.clear(); k.reset_pending.assign(b->B, 0); k.any_reset_pending = false; k.reset_launches = 0;
     k.ragged = false;
     b->mv.seen.start(b->B);

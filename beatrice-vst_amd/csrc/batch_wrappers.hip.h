@@ -783,6 +783,7 @@ static int rb_unbind(BeatriceBatch* b) {
   if (rc) return rc;
   (void)bind_io(b, nullptr, nullptr, 0);
   const bool ragged = r.ragged;
+  b->entries.filling_dropped(b->tk.last_feed_tick, b->tk.plan.count());   // (speaker_entry_plan.h: a step still filling ends with the binding)
   r = {};
   if (ragged) {
     b->silent.on = false;   // (the flags of the ragged steps were the binding's own)
@@ -833,6 +834,7 @@ static bool rb_step(BeatriceBatch* b, const bool synthetic) {
   // hops_fired % H of the step that goes in next -- the steps this call fills take the resident slots from io_host on
   p.cut.put(a);
   int steps = 0, slot = b->io_host;
+  const long long hops_before = r.hops_fired;
   for (int c = 0; c < a.n_chunks; ++c) {
     a.in16_off[c] = (long long)((size_t)slot * B * H + (size_t)(r.hops_fired % H)) * B_IN_HOP;
     if (!a.fires[c]) continue;
@@ -860,7 +862,12 @@ static bool rb_step(BeatriceBatch* b, const bool synthetic) {
     if (!rb_post(b, r.jobs.front())) return false;
     r.jobs.pop_front();
   }
-  for (int i = 0; i < steps; ++i) if (!tick_run(b, true)) return false;   // the full steps: into the pipeline
+  // (speaker_entry_plan.h: a step that an earlier call left filling stays open until its feed is over; a step this call fills alone never is)
+  for (int i = 0; i < steps; ++i) {
+    r.step_open = sentry::step_open_during_feed(hops_before, H, i);
+    if (!tick_run(b, true)) return false;   // the full steps: into the pipeline
+  }
+  r.step_open = sentry::step_open_after_call(r.hops_fired, H);
   if (steps == 0 && H == 1 && !tick_run(b, false)) return false;          // one hop per step: the pipeline advances with every call
   r.hops_done = r.hops_fed();
   if (!synthetic) r.jobs.push_back(BeatriceBatch::ResidentBlocks::Job{call, r.t48, p.dout});
@@ -1363,7 +1370,8 @@ int BeatriceBatch_FlushResidentBlocks(BeatriceBatch* b) {
   const int rc = BeatriceBatch_ConfigureWrapper(b, b->wrap.rate);
   r.on = true;
   if (rc != 0) { r.dead = true; return -2; }
-  r.calls = 0; r.t48 = 0; r.hops_fired = 0; r.hops_done = 0;
+  r.calls = 0; r.t48 = 0; r.hops_fired = 0; r.hops_done = 0; r.step_open = false;
+  b->entries.filling_dropped(b->tk.last_feed_tick, b->tk.plan.count());   // (a hop fired beyond the last full step is gone with its step)
   r.gains.forget();
   b->io_host = 0;   // (hop k of the binding rides in resident slot (k / H) mod io_slots: wrap_post_kernel)
   return 0;

@@ -284,15 +284,23 @@ int BeatriceBatch_MorphSpeakerStaged(BeatriceBatch* b, int slot, int from_slot, 
  * Same weight preparation, same lottery rule (seeded once per batch life, seed + stream), same timeline for the streams that move
  * (additive embedding and odds on the next hop, a four-hop wait, then one key/value block per hop).  All n * 385 spherical means run in
  * one launch and all projections in a second one (results bit-identical to the single-entry calls; a morph entry's codebook is not
- * touched).  In plain tick mode (D: H = 1, 2, 4, with or without the silent-block rule) and in host streaming (E) nothing drains and
- * nothing synchronises: the two launches go onto the batch's stream in front of the next tick and the call returns; in every other mode
- * it drains as the single-entry calls do.  It is a setting, not a mode entry point (no row in the MODES table).
+ * touched).  In plain tick mode (D: H = 1, 2, 4, with or without the silent-block rule), in host streaming (E) and in the wrapper modes
+ * around the ticks (F: BindResidentIO48k, G: BindResidentBlocks, P: BindResidentBlocksRagged) nothing drains and nothing synchronises:
+ * the two launches go onto the batch's stream in front of the next tick and the call returns -- no tick and no wrapper launch is made,
+ * BeatriceBatch_TicksLaunched, BeatriceBatch_ResidentBlocksOwed and the binding's call counter stand; in every other mode it drains as
+ * the single-entry calls do.  It is a setting, not a mode entry point (no row in the MODES table).
+ * In F, G and P "the next hop" of the timeline is the first hop fired by the call that follows: at H = 2 or 4 in F the first block of the
+ * next step; in G the first hop of the next step FED -- a hop that has already fired into a step still filling belongs to that step, and
+ * the step takes the settings in force when its last hop fires and it is fed, which is what BeatriceBatch_SetTargetSpeaker does there.
+ * CONTRACT CHANGE in F, G and P: until now the call drained there, so an entry busy only by rule (b) of BeatriceBatch_SpeakerEntryBusy
+ * was free by the time the call looked; now it is refused with -3 and nothing changes, as in D and E.  The single-entry calls
+ * (BeatriceBatch_MorphSpeaker, MorphSpeakerStaged, UpdateSpeaker) keep draining in every mode.
  * All or nothing.  -1 and no change (no launch, no drain, no seeding): n < 1 or n > max_speakers; the n_weights rules of
  * BeatriceBatch_MorphSpeaker; a slot outside [n_weights, max_speakers); a slot twice; a from_slot twice; a from_slot out of range,
  * equal to its own slot or to another pair's slot.  -3 and no change: some slot is busy (BeatriceBatch_SpeakerEntryBusy).
  * What rotation costs: an entry stays busy until the streams that left it have installed their new key/value blocks (eight hops
- * after the call that moved them, later if the weights move again first) AND, in D and E, until the last step that named it has left
- * the pipeline, BeatriceBatch_TickStages() ticks on.  A stream whose weights move every step therefore needs about TickStages() + 2
+ * after the call that moved them, later if the weights move again first) AND, in D, E, F, G and P, until the last step that named it has
+ * left the pipeline, BeatriceBatch_TickStages() ticks on.  A stream whose weights move every step therefore needs about TickStages() + 2
  * entries to rotate over, at about 3.1 MB of projected tables per entry (four blocks, K and V, in two layouts).  Rewriting an entry
  * that streams are on is not offered; a caller's own tables go into free entries without a drain through
  * BeatriceBatch_InstallSpeakersInFlight. */
@@ -301,11 +309,18 @@ int BeatriceBatch_MorphSpeakersInFlight(BeatriceBatch* b, int n, const int* slot
 /* 1: table entry `entry` is busy, 0: free to be a slot of BeatriceBatch_MorphSpeakersInFlight or an entry of
  * BeatriceBatch_InstallSpeakersInFlight, -1: bad argument.  Busy means (a) some
  * stream's current settings name it -- as target, additive or codebook speaker, or as an installed or pending key/value entry -- or
- * (b) in D and E, a step that named it may still be inside the pipeline: that step's later stages read the entry's additive row and
- * key/value tables.  The bookkeeping is one stamp per entry and errs on the safe side: when the entry's last naming setting goes, it
- * stays busy until BeatriceBatch_TickStages() ticks have been launched counting from the last step the BATCH had been fed at that moment
- * (when it was a key/value install at several hops per step that took the last name away: from the step that installs, whose early hops
- * still run on the blocks installed before), or until the pipeline is drained.  For a stream that takes part in every step that is the
+ * (b) in D, E, F, G and P, a step that named it may still be inside the pipeline: that step's later stages read the entry's additive row
+ * and key/value tables (csrc/speaker_entry_plan.h holds the rule).  CONTRACT CHANGE: in F, G and P the answer used to be 0 here, because
+ * the two in-flight calls drained in those modes; they no longer do, and refuse such an entry with -3.  The ticks count as they are
+ * launched: in P a call launches one tick per FIFO piece in which some stream fires (one idle tick if none), in G at H = 2 or 4 only
+ * when a step is full -- and there an entry whose last name goes while a step is filling (a hop has fired into it, it has not been fed)
+ * stays busy until that step has been fed and has left the pipeline, across BeatriceBatch_Synchronize too; it is released when
+ * BeatriceBatch_FlushResidentBlocks or an unbind drops the filling step.  The bookkeeping is one stamp per entry and errs on the safe
+ * side: when the entry's last naming setting goes, it stays busy until BeatriceBatch_TickStages() ticks have been launched counting from
+ * the last step the BATCH had been fed at that moment (when it was a key/value install at several hops per step that took the last name
+ * away: from the step that installs, whose early hops still run on the blocks installed before -- also when that step's codebook draw,
+ * made behind the install, is what takes the last name: in D and E at H = 2 and 4 this is one tick later than the stamp used to say,
+ * which counted from the step before), or until the pipeline is drained.  For a stream that takes part in every step that is the
  * last step that named the entry; for a stream that changes its settings while it sits out (BeatriceBatch_SetSilentStreams), or that
  * is imported over, it is later than that -- by the steps the batch was fed without it -- or (c) an active morph entry that is
  * itself busy by (a) or (b) lists it with positive odds (with any odds when all of the morph's weights were dropped: the lottery then
@@ -319,9 +334,12 @@ int BeatriceBatch_SpeakerEntryBusy(const BeatriceBatch* b, int entry);
  * at the new entries afterwards with BeatriceBatch_SetTargetSpeaker(s).  All three tables are required (NULL: -1), unlike
  * BeatriceBatch_UpdateSpeaker's optional ones.
  * Two launches per call whatever n is (all tables from staging, all projections).  In plain tick mode (D: H = 1, 2, 4, with or without
- * the silent-block rule) and in host streaming (E) nothing drains and nothing synchronises: the launches go onto the batch's stream in
- * front of the next tick and the call returns; in every other mode it drains first and waits for its launches, as the single-entry call
- * does.  It is a setting, not a mode entry point (no row in the MODES table).
+ * the silent-block rule), in host streaming (E) and in the wrapper modes around the ticks (F, G, P) nothing drains and nothing
+ * synchronises: the launches go onto the batch's stream in front of the next tick and the call returns -- no tick and no wrapper launch
+ * is made, BeatriceBatch_TicksLaunched, BeatriceBatch_ResidentBlocksOwed and the binding's call counter stand; in every other mode it
+ * drains first and waits for its launches, as the single-entry call does.  It is a setting, not a mode entry point (no row in the MODES
+ * table).  CONTRACT CHANGE in F, G and P: the call used to drain there and so succeeded on an entry busy only by rule (b) of
+ * BeatriceBatch_SpeakerEntryBusy; now it returns -3 and changes nothing, as in D and E.
  * The caller's arrays may be reused as soon as the call returns: the call copies them into pinned staging on the calling thread, about
  * 449 KB per entry (tens of microseconds each).  The staging is a ring of 4 calls x BeatriceBatch_MaxInstallEntries() entries, allocated
  * by the first call (29 MB of pinned memory at the cap of 16); a fifth call waits only if the device has not yet run the first one's
